@@ -11,9 +11,13 @@ A step = one pass of the hot path over this rank's genome shard.  Workload (conf
   c2            1,000 genomes x 1M SNPs per GPU                      (configs[1]; fits the 256 MiB L3)
   c5            10,000 genomes x 5,000,000 multi-allelic loci per GPU: the inbreeding sweep (K5 + the estimator named by
                 --algorithm; configs[4]); genomes are independent, so N ranks are N shards with no exchange at all
-One JSON line is printed by rank 0.  At N = 1 the default (c3) run also carries, under "aux", the two other sweeps of
-the path on the same box in the same run -- the 11-bin by-genome sweep (K3) on the C3 population and the inbreeding
-sweep + Simple (K5) on the C5 population -- each with its own roofline and its own CPU baseline (--no-aux skips them).
+One JSON line is printed by rank 0.  A plain run does what the headline figure needs and nothing else: set up, warm up,
+time the K steps, write the outputs (--dump-outputs DIR), print the line.  --full adds everything else the benchmark
+measures or checks: the exchange and AF-epilogue self-check over every row, the dominant kernel alone, the CPU baselines
+and, under "aux", at N = 1 the other sweeps of the path on the same box in the same run -- the 11-bin by-genome sweep
+(K3) on the C3 population, the inbreeding sweep + Simple (K5) on the C5 population, K1 and the window-sized calls --
+each with its own roofline and its own CPU baseline, at N > 1 the strong-scaled C4 job (under --full, --no-cpu-baseline
+and --no-aux skip their part).
 PyTorch is plumbing only (device tensors, RCCL all-reduce).
 """
 from __future__ import annotations
@@ -49,8 +53,13 @@ def parse_args():
     ap.add_argument("--genomes", type=int, default=0, help="override genomes per GPU")
     ap.add_argument("--variants", type=int, default=0, help="override variant rows")
     ap.add_argument("--seed", type=int, default=1111)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-aux", action="store_true", help="skip the K3 / C5 side measurements of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the self-checks, the dominant kernel alone, the CPU baselines, the aux sweeps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (float64; a fixed seeded sample of "
+                         "1,000,000 rows of a per-variant output that has more)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-aux", action="store_true", help="with --full: skip the K3 / C5 side measurements")
     ap.add_argument("--cpu-sample-variants", type=int, default=300_000)      # x 10k genomes = 3e9 cells: ~12 s of the port
     ap.add_argument("--aux-genomes", type=int, default=10_000, help="genomes of the aux C5 population")
     ap.add_argument("--aux-loci", type=int, default=5_000_000, help="loci of the aux C5 population")
@@ -58,7 +67,30 @@ def parse_args():
                     help="total genomes of the strong-scaled aux job of an N > 1 run (default: C4's 100,000 when the headline shape is C3's)")
     ap.add_argument("--algorithm", choices=["Simple", "RitlandLocus", "HallME", "Loglikelihood"], default="Simple",
                     help="estimator of the c5 workload")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:                                  # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_aux = True
+    return args
+
+
+DUMP_ROWS = 1_000_000    # rows of a per-variant output kept by --dump-outputs: [rows][4] counts + [rows] AF in float64 = 40 MB
+DUMP_SEED = 20260        # of the row sample; fixed, so that two builds write the same rows
+
+
+def dump_rows(n_rows):
+    """The rows --dump-outputs keeps of an output of n_rows rows: all of them up to DUMP_ROWS, else a fixed seeded sample in
+    ascending order (the same for every run of the same shape)."""
+    if n_rows <= DUMP_ROWS:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, DUMP_ROWS, replace=False))
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy, float64 (exact for the uint32 counts)."""
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64))
 
 
 def workload_label(args, wl, genomes, variants) -> str:
@@ -619,6 +651,8 @@ def inbreed_workload(args, capi, dist, torch, dev, wl, L, n_gpus, rank):
     achieved = sweep_bytes / (k5_ms * 1e-3) / 1e9
     if rank != 0:
         return None
+    if args.dump_outputs:                              # the last call's LocusResults of rank 0's genomes, a column per field
+        dump_outputs(args.dump_outputs, {name: res[name] for name in res.dtype.names})
     return {
         "metric": "genomes·loci/sec (inbreeding sweep + " + args.algorithm + ")",
         "value": n_gpus * G * L * args.steps / elapsed,
@@ -765,20 +799,23 @@ def main():
         region_ms = [e0.elapsed_time(e1) for e0, e1 in region_events]
         region_events = None
         counts = bufs[(issued[0] - 1) % len(bufs)]                        # the last batch's (summed) counts
-        # Exchange self-check outside the timed region, on the device, over EVERY variant and on every rank: the four summed
-        # counts of a row cover every genome of every rank exactly once; and the AF epilogue read those sums.
-        row_ok = counts.sum(dim=1, dtype=torch.int64) == total_genomes
-        # (divided by a TENSOR: torch turns a division by a Python scalar into a multiplication by its reciprocal on the
-        # device, which rounds differently from the IEEE division the epilogue and the reference make)
-        want_af = (counts[:, 1].to(torch.float64) + 2.0 * counts[:, 2].to(torch.float64)) / torch.full((), 2.0 * total_genomes, dtype=torch.float64, device=dev)
-        checks = torch.stack([row_ok.all(), (af == want_af).all()]).to(torch.int32)
-        del row_ok, want_af
+        # Exchange self-check (--full) outside the timed region, on the device, over EVERY variant and on every rank: the four
+        # summed counts of a row cover every genome of every rank exactly once; and the AF epilogue read those sums.
+        checks = None
+        if args.full:
+            row_ok = counts.sum(dim=1, dtype=torch.int64) == total_genomes
+            # (divided by a TENSOR: torch turns a division by a Python scalar into a multiplication by its reciprocal on the
+            # device, which rounds differently from the IEEE division the epilogue and the reference make)
+            want_af = (counts[:, 1].to(torch.float64) + 2.0 * counts[:, 2].to(torch.float64)) / torch.full((), 2.0 * total_genomes, dtype=torch.float64, device=dev)
+            checks = torch.stack([row_ok.all(), (af == want_af).all()]).to(torch.int32)
+            del row_ok, want_af
         # per rank: the mean launch of the dominant kernel inside the region, and the region's own wall time -- their spread over the
         # ranks shows a straggler, and (step time - sweep time) what of the exchange and the epilogue is NOT hidden beside the sweeps
         kernel_mean = float(np.mean(region_ms)) if region_ms else 0.0
         spread = {"kernel_ms_min": kernel_mean, "kernel_ms_max": kernel_mean, "step_ms_min": elapsed / args.steps * 1e3, "step_ms_max": elapsed / args.steps * 1e3}
         if n_gpus > 1:
-            dist.all_reduce(checks, op=dist.ReduceOp.MIN)                  # every rank must agree
+            if checks is not None:
+                dist.all_reduce(checks, op=dist.ReduceOp.MIN)              # every rank must agree
             lo = torch.tensor([kernel_mean, elapsed / args.steps * 1e3], dtype=torch.float64, device=dev)
             hi = lo.clone()
             dist.all_reduce(lo, op=dist.ReduceOp.MIN)
@@ -788,12 +825,14 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         spread["exposed_exchange_and_epilogue_ms"] = spread["step_ms_max"] - spread["kernel_ms_max"]
-        exchange_ok, af_ok = (bool(x) for x in checks.tolist())
+        exchange_ok, af_ok = (bool(x) for x in checks.tolist()) if checks is not None else (None, None)
 
-        # ... and the same kernel alone, back to back into a scratch buffer (a cross-check of the figure above).
-        scratch = torch.empty((V, 4), dtype=torch.int32, device=dev)
-        ms = pop.allele_count_timed(scratch.data_ptr(), stream, 2, max(args.steps, 10))
-        del scratch
+        # ... and (--full) the same kernel alone, back to back into a scratch buffer (a cross-check of the figure above).
+        ms = None
+        if args.full:
+            scratch = torch.empty((V, 4), dtype=torch.int32, device=dev)
+            ms = pop.allele_count_timed(scratch.data_ptr(), stream, 2, max(args.steps, 10))
+            del scratch
         job = dict(total_genomes=total_genomes, G=G, elapsed=elapsed, exchange_ok=exchange_ok, af_ok=af_ok, ms=region_ms, ms_alone=ms, t_synth=t_synth, spread=spread,
                    sweep_bytes=pop.sweep_bytes)                           # V*ceil(G/4) + 16*V
         if keep_population:
@@ -827,6 +866,14 @@ def main():
     k2_ms = float(np.mean(ms))                                         # the average launch of the timed region
     achieved = sweep_bytes / (k2_ms * 1e-3) / 1e9
 
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the step receives from its last call: the (summed) [V][4] counts and the AF column
+        rows = dump_rows(V)
+        index = None if rows is None else torch.from_numpy(rows).to(dev)
+        kept_counts, kept_af = (counts, af) if index is None else (counts[index], af[index])
+        dump_outputs(args.dump_outputs, {"allele_counts": kept_counts.cpu().numpy().view(np.uint32), "allele_frequency": kept_af.cpu().numpy()})
+        del index, kept_counts, kept_af
+
     result = None
     if rank == 0:
         value = total_genomes * V * args.steps / elapsed
@@ -854,8 +901,9 @@ def main():
                 "variants": V,
                 "layout": "2-bit dosage rows, variant-major",
                 "exchange": exchange_description(),
-                "exchange_check": f"row sums == total genomes on all {V} variants, on every rank: " + ("ok" if exchange_ok else "MISMATCH")
-                                  + "; AF epilogue == (het + 2 hom) / 2G on all of them: " + ("ok" if job["af_ok"] else "MISMATCH"),
+                "exchange_check": (f"row sums == total genomes on all {V} variants, on every rank: " + ("ok" if exchange_ok else "MISMATCH")
+                                   + "; AF epilogue == (het + 2 hom) / 2G on all of them: " + ("ok" if job["af_ok"] else "MISMATCH")
+                                   if args.full else "not run (--full checks the row sums and the AF epilogue on every variant)"),
                 "distributed": distributed_config(job),
                 "scaling_series": ("weak: " + str(G) + " genomes per GPU at every N; this line is its N = " + str(n_gpus) + " point"
                                    if scaling == "weak" else "strong: " + str(total_genomes) + " genomes split over the ranks"),
@@ -874,8 +922,9 @@ def main():
                 "algorithmic_bytes_per_launch": sweep_bytes,
                 "kernel_ms": k2_ms,
                 "kernel_ms_statistic": (f"mean of the {len(ms)} launches of the timed region (HIP events on the launch stream around each); "
-                                        f"median {float(np.median(ms)):.3f}, min {float(np.min(ms)):.3f}; the kernel alone, back to back into a "
-                                        f"scratch buffer after the region: median {float(np.median(job['ms_alone'])):.3f}"),
+                                        f"median {float(np.median(ms)):.3f}, min {float(np.min(ms)):.3f}"
+                                        + (f"; the kernel alone, back to back into a scratch buffer after the region: "
+                                           f"median {float(np.median(job['ms_alone'])):.3f}" if job["ms_alone"] is not None else "")),
             },
         }
         dense, nv = None, 0

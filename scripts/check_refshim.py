@@ -5,20 +5,25 @@ The GPU packages compile against the reference's own headers inside its tree (-D
 the shim here, where the reference cannot be built.  Nothing compiles both; this script is the next best thing: for
 every public member function a shim class declares it looks for a member of the same name in the mirrored reference
 class and compares the normalised signatures -- return type, parameter types, const -- so that a package written
-against the shim meets the same declarations in the reference tree.  Runs only where /root/reference exists (the build
-container); tests/test_refshim_cpu.py runs it and fails on anything not listed, with its reason, in ACCEPTED.
+against the shim meets the same declarations in the reference tree.  It needs a checkout of the reference (--reference)
+and fails on anything not listed, with its reason, in ACCEPTED.  A run without problems records what it verified -- every
+declaration of the shim that it compared, as the shim spells it -- in tests/golden/refshim_verified.json (--record);
+tests/test_refshim_cpu.py holds the shim to that record, so a changed shim declaration fails there until this check has
+passed on it again and the record is renewed.
 
-  python scripts/check_refshim.py [--reference /root/reference] [--report docs/refshim_check.txt]
+  python scripts/check_refshim.py --reference <KGL_Gene checkout> [--report docs/refshim_check.txt] [--record]
 """
 from __future__ import annotations
 
 import argparse
+import json
 import re
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 SHIMS = [ROOT / "kgl_gene_amd/csrc/host/kgx_refshim.h", ROOT / "kgl_gene_amd/csrc/host/kgx_pf7_resources.h"]
+RECORD = ROOT / "tests/golden/refshim_verified.json"
 
 # shim class -> (reference header, reference class)
 MIRRORS = {
@@ -156,8 +161,36 @@ def members(body: str, is_struct: bool) -> dict[str, set[str]]:
     return found
 
 
+def enumerators(enum: str, text: str):
+    m = re.search(r"\benum\s+class\s+" + enum + r"\b[^{]*\{([^}]*)\}", text)
+    return None if not m else [e.split("=")[0].strip() for e in m.group(1).split(",") if e.strip()]
+
+
+def shim_text_without_comments() -> str:
+    return "\n".join(strip_comments(p.read_text()) for p in SHIMS if p.exists())
+
+
+def shim_declarations() -> list[list]:
+    """[class, member, what the shim declares] for everything check() compares, from the shim alone and in check()'s order:
+    the public member functions of the mirrored classes with their normalised signatures, the enumerators with their
+    positions, the constants the packages use."""
+    shim_text = shim_text_without_comments()
+    out = []
+    for shim_class in MIRRORS:
+        body = class_body(shim_text, shim_class)
+        if body is None:
+            continue
+        is_struct = re.search(r"\bstruct\s+" + shim_class + r"\b", shim_text) is not None
+        out += [[shim_class, name, sorted(signatures)] for name, signatures in sorted(members(body, is_struct).items()) if name != shim_class]
+    for enum in ENUMS:
+        out += [[enum, e, [f"enumerator {position}"]] for position, e in enumerate(enumerators(enum, shim_text) or [])]
+    for holder, (_, names) in CONSTANTS.items():
+        out += [[holder, name, ["constant"]] for name in names if re.search(r"\b" + name + r"\b", shim_text)]
+    return out
+
+
 def check(reference: Path):
-    shim_text = "\n".join(strip_comments(p.read_text()) for p in SHIMS if p.exists())
+    shim_text = shim_text_without_comments()
     rows, problems = [], []
     for shim_class, (header, ref_class) in MIRRORS.items():
         body = class_body(shim_text, shim_class)
@@ -187,10 +220,7 @@ def check(reference: Path):
             if status in ("MISSING in the reference", "DIFFERENT"):
                 problems.append((shim_class, name, f"{status}: shim {sorted(signatures)} vs {header} {sorted(theirs.get(name, []))}"))
     for enum, header in ENUMS.items():
-        def enumerators(text):
-            m = re.search(r"\benum\s+class\s+" + enum + r"\b[^{]*\{([^}]*)\}", text)
-            return None if not m else [e.split("=")[0].strip() for e in m.group(1).split(",") if e.strip()]
-        mine, theirs = enumerators(shim_text), enumerators(strip_comments((reference / header).read_text()))
+        mine, theirs = enumerators(enum, shim_text), enumerators(enum, strip_comments((reference / header).read_text()))
         if mine is None or theirs is None:
             problems.append((enum, "*", f"enum not found (shim: {mine is not None}, {header}: {theirs is not None})"))
             continue
@@ -212,12 +242,13 @@ def check(reference: Path):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reference", default="/root/reference")
+    ap.add_argument("--reference", required=True, help="a checkout of the reference (KGL_Gene)")
     ap.add_argument("--report", default="")
+    ap.add_argument("--record", action="store_true", help="after a run without problems, renew tests/golden/refshim_verified.json")
     args = ap.parse_args()
     reference = Path(args.reference)
-    if not reference.exists():
-        sys.exit(f"{reference} does not exist: this check runs in the build container only")
+    if not reference.is_dir():
+        sys.exit(f"{reference} is not a directory: this check needs a checkout of the reference")
     rows, problems = check(reference)
     lines = [f"{c}::{n}: {s}" + ("" if s == "same" else f"\n    shim      {a}\n    reference {b} ({h})" + (f"\n    accepted: {ACCEPTED[(c, n)]}" if (c, n) in ACCEPTED else ""))
              for c, n, s, a, b, h in rows]
@@ -229,6 +260,10 @@ def main():
     print(text)
     for shim_class, name, what in problems:
         print(f"PROBLEM {shim_class}::{name}: {what}")
+    if args.record and not problems:
+        verified = [[c, n, a] for c, n, _, a, _, _ in rows]
+        assert verified == shim_declarations(), "shim_declarations() and check() disagree about what the shim declares"
+        RECORD.write_text(json.dumps({"summary": summary, "verified": verified}, indent=1) + "\n")
     sys.exit(1 if problems else 0)
 
 

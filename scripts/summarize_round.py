@@ -47,7 +47,7 @@ traffic_db_path = dst / "traffic.json"
 traffic_db = json.loads(traffic_db_path.read_text()) if traffic_db_path.exists() else {}
 lines = [f"# rocprofv3 summary `{tag}` — the default `bench.py` run (N=1)", "",
          f"Commands (on the GPU box, `scripts/profile_round.sh {tag}`):",
-         "`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline`,",
+         "`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline`,",
          "then the same command (`--steps 3 --warmup 1`) once under `--pmc FETCH_SIZE` and once under `--pmc WRITE_SIZE`.", "",
          "| sweep | kernel | calls | avg ms (rocprofv3) | ms (HIP events, bench.py) | algorithmic bytes | GB/s (rocprofv3 avg) | of 8 TB/s | HBM read = 2 x FETCH_SIZE x 1024 | HBM write = WRITE_SIZE x 1024 | traffic / algorithmic |",
          "|---|---|---|---|---|---|---|---|---|---|---|"]

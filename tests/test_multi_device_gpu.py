@@ -374,7 +374,7 @@ def test_bench_two_ranks_rehearsal_on_one_device(tmp_path, workload):
         env.pop(key, None)
     shape = ["--genomes", "3000", "--variants", "300000", "--c4-genomes", "5001"] if workload == "c3" else ["--workload", "c5", "--genomes", "1500", "--variants", "100000"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
-           "29541" if workload == "c3" else "29542", str(root / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", *shape]
+           "29541" if workload == "c3" else "29542", str(root / "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", *shape]
     res = subprocess.run(cmd, env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [line for line in res.stdout.splitlines() if line.startswith("{")]
