@@ -368,8 +368,8 @@ double kgx_inbreed_last_sweep_ms(void);
  * sweep): the sweep without the per-locus helper kernels (tables, entries, segment defaults). */
 double kgx_inbreed_last_kernel_ms(void);
 /* Where the most recent successful kgx_inbreed call ran on per-genome moments (HallME, Loglikelihood over more than 8192
- * loci): device time of its class passes over the genotype bytes (one per class of homozygous cell, with the merges of
- * their items) and of the kernel that then iterates / searches on the moments; 0 otherwise. */
+ * loci): device time of its class passes (ONE pass over the genotype bytes that leaves every class's hits as bit rows, then
+ * per class of homozygous cell the moments from those rows and the merge of its items) and of the kernel that then iterates / searches on the moments; 0 otherwise. */
 double kgx_inbreed_last_moments_ms(void);
 double kgx_inbreed_last_search_ms(void);
 /* Objective evaluations the most recent KGX_ALGO_LOGLIKELIHOOD call needed (the most any genome made; where the call
@@ -379,7 +379,7 @@ int kgx_inbreed_last_evaluations(void);
 #define KGX_PATH_NONE                       0
 #define KGX_PATH_FREQUENCY_SWEEP            1   /* Simple, RitlandLocus: the one sweep every estimator starts with            */
 #define KGX_PATH_ONE_LAUNCH                 2   /* HallME / Loglikelihood, <= 8192 loci: the whole iteration in one launch     */
-#define KGX_PATH_HALL_MOMENTS               3   /* HallME on per-genome moments (one pass per class of homozygous cell)        */
+#define KGX_PATH_HALL_MOMENTS               3   /* HallME on per-genome moments (the classes' hits from ONE pass over the bytes) */
 #define KGX_PATH_HALL_PASSES                4   /* HallME by 50 passes over the bytes                                          */
 #define KGX_PATH_LOGLIK_MOMENTS             5   /* Loglikelihood on the same moments + the exact walk next to the floor        */
 #define KGX_PATH_LOGLIK_MOMENTS_AND_PASSES  6   /* ... and passes for the genomes the statistics could not serve               */

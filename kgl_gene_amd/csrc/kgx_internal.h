@@ -96,6 +96,10 @@ struct ScratchPlan {
   }
 };
 int scratch_reserve(Device& dev, size_t bytes, char** out);
+// A grow-only device buffer kept between calls beside the arena (the hits' words, the classes' bit rows, a compaction level): at
+// least `want` bytes behind p afterwards.  Grown by freeing first and only where `want + headroom` bytes are free; where that
+// fails p is null, bytes 0, HIP's error cleared and nothing reported (non-zero return): the caller has a path without the buffer.
+int grow_device_buffer(char*& p, size_t& bytes, size_t want, size_t headroom);
 // ... and a page-locked host buffer of the device (which: 0 inputs, 1 results), grown when needed; the caller holds the mutex.
 int pinned_reserve(Device& dev, int which, size_t bytes, char** out);
 

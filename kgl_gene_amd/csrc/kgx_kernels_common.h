@@ -6,13 +6,8 @@
 #include <type_traits>
 #include <stdint.h>
 
+#include "kgx_inbreed_constants.h"   // kWave, kBlock and the sizes the host-only plan of an inbreeding call shares with the kernels
+
 typedef uint32_t kgx_v4u __attribute__((ext_vector_type(4)));
-
-namespace kgx {
-
-constexpr int kWave = 64;            // CDNA wavefront
-constexpr int kBlock = 256;          // 4 waves per workgroup
-
-}  // namespace kgx
 
 #endif  // KGX_KERNELS_COMMON_H

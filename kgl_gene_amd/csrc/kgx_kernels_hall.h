@@ -1,4 +1,6 @@
-// HallME over a large call without 50 passes over the genotype bytes (driven from kgx_inbreed.hip: inbreed_shard, `hall_moments`).
+// HallME over a large call without 50 passes over the genotype bytes (driven from kgx_inbreed.hip:
+// InbreedCall::gather_moments -- order_classes, reserve_hits, class_passes -- and hall_by_moments; planned as `hall_candidate` in
+// kgx_inbreed_plan.h).
 //
 // processHallME's step (_calc.cpp:255-285) is  F <- F * S(F) / N  with  S(F) = sum over the genome's homozygous cells of
 // 1 / (F + (1-F)*y),  y = the frequency of the cell's allele at its locus (classify_cell: f1).  The cells enter S only
@@ -25,23 +27,18 @@
 
 namespace kgx {
 
-constexpr int kHallMoments = 5;                          // M0 (a count) .. M4
-constexpr int kHallKeyMantissa = 7;
-constexpr int kHallMinExponent = -20;                    // bins reach down to y = 2^-20; below (and above 1) the call takes the 50 passes
-constexpr uint32_t kHallBins = 1u + static_cast<uint32_t>(-kHallMinExponent) * (1u << kHallKeyMantissa) + 1u;   // {0}, [2^-20, 1), {1 ..}
+// (kHallMoments, kHallKeyMantissa, kHallMinExponent, kHallBins, kHallItemLoci, kHallBlockLoci, HallRecord -- one locus of a class, in
+// bin order -- and the bit rows' spans: kgx_inbreed_constants.h, shared with the host-only plan of a call)
 constexpr uint32_t kHallNoKey = 0xFFFu;                  // sorts behind every bin (12-bit keys)
-constexpr uint32_t kHallItemLoci = 2048;                 // (an item's digit image: 64 KB of the matrix-core pass's LDS; 1024: more items to merge, 4096: one workgroup a CU)
 constexpr int kHallBinsPerThread = (kHallBins + kBlock - 1) / kBlock;
 static_assert(kHallBins < kHallNoKey, "12-bit sort keys");
 
-struct HallRecord { uint32_t row; uint32_t bin; double delta; };          // one locus of a class, in bin order: the row it reads, its y = centre(bin) + delta
 struct HallItem { uint32_t begin, end, bin, pad; };                       // positions [begin, end) of the sorted order
 // Every item's loci are also laid out in BLOCKS of kHallBlockLoci slots (k_hall_pad: item i's records from slot
 // 64 * item_block_base[i], its last block filled up with slots that match nothing), which is what the class pass walks.
 // Loglikelihood on the same moments (kgx_kernels_loglik.h) also wants, for the bins its 1e-10 floor can come near, WHICH of
 // a bin's loci a genome is homozygous at: the class pass can leave one bit per (slot, genome), a block's 64 slots to a
-// word (hall_word_index).  Those bins are the lowest, so their blocks are the first.
-constexpr uint32_t kHallBlockLoci = 64;
+// word (hall_word_index).  Those bins are the lowest, so their blocks are the first.  (kHallBlockLoci = 64)
 // where genome g's word of block b sits: a lane of the class pass owns 8 genomes and stores their words of a block as four
 // 16-byte pairs, pair q of all lanes together (1 KB a wave-store): [block][pair][lane][2].  lanes = words_per_block / 8.
 __host__ __device__ inline uint64_t hall_word_index(uint64_t block, uint64_t g, uint64_t lanes) {
@@ -393,9 +390,7 @@ struct HallClassRows { uint64_t base[16]; };                               // wh
 // l, l + 64, .. l + 448 (eight coalesced loads a locus) -- genomes 4 (l + 64 d) + b for dword d, byte b -- and keeps the flag
 // of (d, b) in bit 8 b + d of ONE dword: no gathering of flags inside a dword, just the eight hit masks shifted onto each
 // other.  So byte o = 4 l + b of a span holds, in bit q, genome o + 256 q of the span (hall_bits_genome).
-constexpr uint64_t kBitsSpanGenomes = 2048;
-constexpr uint64_t kBitsSpanBytes = kBitsSpanGenomes / 8;
-__host__ __device__ inline uint64_t hall_bit_row_bytes(uint64_t n_genomes) { return (n_genomes + kBitsSpanGenomes - 1) / kBitsSpanGenomes * kBitsSpanBytes; }
+// (kBitsSpanGenomes = 2048, kBitsSpanBytes and hall_bit_row_bytes: kgx_inbreed_constants.h)
 // the genome (of the call) in bit q of byte `at` of a bit row
 __device__ __forceinline__ uint64_t hall_bits_genome(uint64_t at, uint32_t q) { return (at / kBitsSpanBytes) * kBitsSpanGenomes + at % kBitsSpanBytes + 256u * q; }
 

@@ -314,9 +314,8 @@ k_inbreed_sweep(const uint32_t* __restrict__ gt, uint64_t dwords_per_row, uint64
 #define KGX_EVAL_DEPTH3 2           // ... modes 1, 3, 4, which have the registers for it
 #endif
 struct alignas(16) EvalEntry { double y, d; };
-constexpr int kEvalBatch = 8;
 constexpr uint32_t kEvalSlots = 160;
-constexpr uint64_t kRitlandSegment = 4088;        // MODE 3: loci per segment, below the 12-bit class counters' range
+// (kEvalBatch, and kRitlandSegment -- MODE 3: loci per segment, below the 12-bit class counters' range: kgx_inbreed_constants.h)
 constexpr uint32_t kOddCell = 1u << 28;           // MODE 3: in the entry's hi word: one more odd cell (a 4-bit count per batch)
 // ... and what is odd about it, in the entry's lo word (bits the 12-bit class counters never reach):
 constexpr uint32_t kOddMinus = 1u << 24;          // unclassified carrier at a locus with defaults: its class frequencies come off
@@ -1577,7 +1576,7 @@ __device__ __forceinline__ BrentState brent_start(const unsigned long long* __re
 //   a = best point, fx = its value;  b = worst point, fw = its value;  v = reflected point, fv = its value;
 //   u = the point to evaluate next;  widened = phase;  e = evaluations so far;  x = the result once done.
 enum : int { kNmFirst = 0, kNmSecond, kNmReflect, kNmExpand, kNmOutside, kNmInside };
-constexpr int kSearchBrent = 0, kSearchNelderMead = 1;
+// (kSearchBrent = 0, kSearchNelderMead = 1, and below kSearchNelderMeadPair = 2: kgx_inbreed_constants.h)
 __device__ __forceinline__ void nm_first_simplex(double x0, double& xa, double& xb) {
   auto clampx = [](double x) { return x > 1.0 ? 1.0 : (x < -1.0 ? -1.0 : x); };
   const double step = (1.0 - -1.0) * 0.25;
@@ -1643,7 +1642,6 @@ __device__ __forceinline__ void nm_advance(BrentState& s, double f) {      // f:
 // search would have seen, in its order: the same path, the same result, in about half the passes over the bytes.
 //   u, d = the two points to evaluate next;  e counts the evaluations the one-at-a-time search would have made.
 enum : int { kNm2Start = 0, kNm2Reflect, kNm2Expand, kNm2Outside };
-constexpr int kSearchNelderMeadPair = 2;
 __device__ __forceinline__ BrentState nm2_start(double x0) {
   BrentState s{};
   nm_first_simplex(x0, s.a, s.b);
@@ -1772,8 +1770,7 @@ k_gather_states(const BrentState* __restrict__ st, const double* __restrict__ f,
 // unrolled per-thread loops: with one or two waves on a SIMD a pass costs the latency of its dependent instructions,
 // and a cell past the selection would cost as much as a real one (it contributes +0.0 / a factor 1.0: leaving it out
 // gives the bitwise-same sums).
-constexpr int kGenomeLoci = 8192;                        // a block per genome: 32 cells per thread; a wave per genome: up to kGenomeWaveLoci
-constexpr int kGenomeWaveLoci = 2048;
+// (kGenomeLoci = 8192 -- a block per genome: 32 cells per thread -- and kGenomeWaveLoci = 2048, a wave per genome: kgx_inbreed_constants.h)
 
 // A double moved between the lanes of a row of 16 by a DPP control (two v_mov_b32_dpp: a few cycles, where the
 // ds_bpermute pair behind __shfl_xor takes an LDS round trip -- and the passes here are nothing but such latencies).

@@ -1,5 +1,6 @@
 // Loglikelihood over a large call without a pass over the genotype bytes per evaluation (driven from kgx_inbreed.hip:
-// inbreed_shard, `loglik_moments`).  The reference's objective (logLikelihood, kga_analysis_inbreed_calc.cpp:94-129) is, per genome,
+// InbreedCall::gather_moments -- order_classes, reserve_hits, class_passes -- and loglik_by_moments; planned as `loglik_candidate`
+// in kgx_inbreed_plan.h).  The reference's objective (logLikelihood, kga_analysis_inbreed_calc.cpp:94-129) is, per genome,
 //     sum over homozygous cells of log clamp(F*y + (1-F)*y*y)  +  sum over heterozygous cells of log clamp(2*(1-F)*f1*f2),
 // clamp = to [1e-10, 1], y the frequency of the cell's allele.  nlopt's Nelder-Mead evaluates it ~55 times per genome
 // (processLogLikelihood, :153-216); as table passes that is 38 sweeps over the matrix (two values per sweep).  Here:

@@ -168,6 +168,21 @@ int scratch_reserve(Device& dev, size_t bytes, char** out) {
   return KGX_OK;
 }
 
+int grow_device_buffer(char*& p, size_t& bytes, size_t want, size_t headroom) {
+  if (bytes >= want) return KGX_OK;
+  if (p) (void)hipFree(p);
+  p = nullptr;
+  bytes = 0;
+  size_t free_bytes = 0, total_bytes = 0;
+  if (hipMemGetInfo(&free_bytes, &total_bytes) != hipSuccess || free_bytes < want + headroom || hipMalloc(&p, want) != hipSuccess) {
+    (void)hipGetLastError();
+    p = nullptr;
+    return KGX_ENOMEM;
+  }
+  bytes = want;
+  return KGX_OK;
+}
+
 int pinned_reserve(Device& dev, int which, size_t bytes, char** out) {
   if (bytes > dev.pinned_bytes[which]) {
     if (dev.pinned[which]) (void)hipHostFree(dev.pinned[which]);

@@ -88,7 +88,13 @@ def test_constants_match_the_header():
     import re
     from pathlib import Path
 
-    text = (Path(__file__).resolve().parent.parent / "kgl_gene_amd" / "csrc" / "kgx_kernels_hall.h").read_text()
+    # the moments' kernels take the sizes that the host-only plan of a call shares with them from the constants header:
+    # each is defined in exactly one of the two (moved, not restated), with the value this file restates
+    csrc = Path(__file__).resolve().parent.parent / "kgl_gene_amd" / "csrc"
+    text = (csrc / "kgx_inbreed_constants.h").read_text() + (csrc / "kgx_kernels_hall.h").read_text()
+    assert '#include "kgx_inbreed_constants.h"' in (csrc / "kgx_kernels_common.h").read_text()     # (which every kernel header includes)
+    for name in ("kHallMoments", "kHallKeyMantissa", "kHallMinExponent", "kHallNoKey"):
+        assert len(re.findall(rf"constexpr \w+ {name} = ", text)) == 1, name
     assert int(re.search(r"kHallMoments = (\d+);", text).group(1)) == MOMENTS
     assert int(re.search(r"kHallKeyMantissa = (\d+);", text).group(1)) == KEY_MANTISSA
     assert int(re.search(r"kHallMinExponent = (-?\d+);", text).group(1)) == MIN_EXPONENT

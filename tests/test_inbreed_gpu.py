@@ -1056,3 +1056,52 @@ def test_offsets_with_more_than_fourteen_alts_vs_oracle(kgx, algorithm):
                             algorithm, phased=True)[0][order]
     assert np.array_equal(batch["total_allele_count"], got["total_allele_count"])
     m.close()
+
+
+@pytest.mark.gpu
+def test_four_genomes_per_lane_keeps_loglikelihood_off_the_moments(kgx, monkeypatch):
+    """KGX_K5_EVAL_GPL=4 (scripts/tune_k5.sh sets it): the class pass of four genomes per lane (k_hall_sweep<4, false>) writes no
+    hits' words, and the Loglikelihood search on moments reads them -- so the plan (kgx_inbreed_plan.h: loglik_candidate) sends
+    such a call to the passes.  9000 loci: past the one-launch size (8192).  The call under the switch IS the call by passes
+    (KGX_K7_LL_PASSES=1 on top of it changes nothing: every field bit for bit); its counts are the default call's, which runs on
+    the moments.  HallME reads no words: it keeps its moments under the switch, within the 1e-10 of
+    test_hallme_by_moments_is_the_fifty_passes of its 50 passes."""
+    G, L = 520, 9000
+    m = kgx.GenotypeMatrix(G, L)
+    table = m.synth_multiallelic(1111, 0, 0)
+    counts = ["major_hetero_count", "minor_hetero_count", "minor_homo_count", "major_homo_count", "total_allele_count"]
+
+    def call(algorithm, g0, env):
+        for name, value in env.items():
+            monkeypatch.setenv(name, value)
+        start = kgx.reference_starts(algorithm, START_SEED, G - g0)
+        fields = {k: v.copy() for k, v in _fields(m.inbreed(table, algorithm, phased=True, g0=g0, g1=G, start=start)).items()}
+        path = kgx.inbreed_last_path()
+        for name in env:
+            monkeypatch.delenv(name)
+        return fields, path
+
+    for g0 in (0, 8):
+        default, default_path = call("Loglikelihood", g0, {})
+        assert default_path == "loglik moments", (g0, default_path)
+        narrow, narrow_path = call("Loglikelihood", g0, {"KGX_K5_EVAL_GPL": "4"})
+        assert narrow_path == "loglik passes", (g0, narrow_path)
+        passes, passes_path = call("Loglikelihood", g0, {"KGX_K5_EVAL_GPL": "4", "KGX_K7_LL_PASSES": "1"})
+        assert passes_path == "loglik passes", (g0, passes_path)
+        for name in narrow:
+            assert narrow[name].tobytes() == passes[name].tobytes(), (g0, name)
+        for name in counts:
+            assert narrow[name].tobytes() == default[name].tobytes(), (g0, name)
+        assert np.isfinite(narrow["inbred_allele_sum"]).all() and np.abs(narrow["inbred_allele_sum"]).max() > 0.05, g0   # (a search did run)
+
+        moments, moments_path = call("HallME", g0, {"KGX_K5_EVAL_GPL": "4"})
+        assert moments_path == "hall moments", (g0, moments_path)
+        fifty, fifty_path = call("HallME", g0, {"KGX_K5_EVAL_GPL": "4", "KGX_K7_HALL_PASSES": "1"})
+        assert fifty_path == "hall passes", (g0, fifty_path)
+        for name in counts:
+            assert np.array_equal(moments[name], fifty[name]), (g0, name)
+        a, b = moments["inbred_allele_sum"], fifty["inbred_allele_sum"]
+        assert np.array_equal(np.isfinite(a), np.isfinite(b)), g0
+        err = np.abs(a - b)[np.isfinite(b)]
+        assert err.max(initial=0.0) <= 1e-10, (g0, float(err.max(initial=0.0)))
+    m.close()
