@@ -13,6 +13,7 @@ import pytest
 from . import inbreed_inputs as ii
 from . import oracle_api as oa
 from . import synth_vcf as sv
+from .loglik_populations import build
 
 pytestmark = pytest.mark.gpu
 
@@ -29,16 +30,6 @@ def seeded_starts(kgx, algorithm, seed, order):
     start = np.empty(len(order), dtype=np.float64)
     start[order] = kgx.reference_starts(algorithm, seed, len(order))
     return start
-
-
-def build(G, L, mode, seed):
-    rec, gt = sv.multiallelic_block(G, L, rng_seed=seed, missing_af_frac=0.03, dup_records=60)   # repeated records: same-phase pairs, >= 3 variants
-    ids = sv.genome_ids(G)
-    ref = oa.Population("gnomad")
-    ref.add_genomes(["Reference"])
-    ref.add_records(rec, None, oa.Population.REFERENCE)
-    dip = sv.oracle_population(rec, gt, ids, mode)
-    return rec, gt, ids, ref.filter_snp_pass(), dip
 
 
 def test_class_frequency_table_is_bit_exact(kgx):
