@@ -236,6 +236,68 @@ int kgx_unique_phased_counts(kgx_pop* pop, const uint8_t* bin_of_variant, uint32
 int kgx_genome_row_lists(kgx_pop* pop, uint64_t g0, uint64_t g1, const uint8_t* row_selected /* or NULL */, uint64_t* begin,
                          uint32_t* rows /* or NULL */, uint64_t capacity);
 
+/* ---- Gene genotype tables: the gene-variant analysis of the PfEMP package (kga_analytic/kga_PfEMP/kga_analysis_PfEMP_variant.{h,cpp};
+ *      callers kga_analysis_PfEMP.cpp:100-103,136-144).  For every gene the reference walks every genome through std::map lookups
+ *      and writes one CSV line (writeGeneResults, _variant.cpp:109-233).  All of that line follows from
+ *        (1) a per-(gene, genome) GENOTYPE HASH: GenotypeAnalysis::genotypeHash (_variant.cpp:453-484) sums Utility::hash(HGVS) over
+ *            the distinct variants the genome carries in the gene, in size_t; the sum is order-free, so
+ *            hash[gene][g] = sum over the gene's rows r with code(g, r) != 0 of row_key[r], mod 2^64 -- the reference's value to the bit;
+ *        (2) a per-gene CENSUS of those hashes (GenotypeAnalysis::analyzeGenePopulation, :401-450): the distinct values and how
+ *            many genomes hold each.
+ *      Genes are row lists, the convention of kgx_compound_offsets_listed: gene i = rows member_rows[first_member[i] .. + n_rows[i]);
+ *      rows need not be adjacent or ascending, genes may share rows, n_rows[i] == 0 is allowed.  A row listed twice in one gene, a
+ *      row >= n_variants or n_members > 2^32: KGX_EINVAL.  Which rows belong to a gene (the GFF model, ContigModifyFilter's
+ *      margin) is the caller's business.
+ *      A genome CARRIES a row when its code is 1, 2 or 3.  A genome carrying no row of the gene is zero-variant
+ *      (GenotypeAnalysis::zeroVariants); every other genome has a genotype EVEN WHEN ITS HASH IS 0 (the test is the carried count).
+ *      Two genomes with different row sets and equal sums are one genotype, as in the reference ("A bit dodgy, there may be hash
+ *      collisions", _variant.cpp:475).  Honours the genome mask: a masked-out genome is neither zero-variant nor a genotype nor a
+ *      carrier for the singleton counts; its hash / counts entries read 0.
+ *      Works over any binding: every shard hashes its own genomes on its device, the census runs over all genomes of the
+ *      population on the first shard's device; the results do not depend on the binding. */
+typedef struct kgx_gene_census {
+  uint64_t genomes;               /* genomes taking part (all, or those the genome mask keeps)            */
+  uint64_t zero_variant_genomes;  /* of those, genomes carrying no row of the gene (zeroVariants())       */
+  uint64_t genotypes;             /* distinct hashes among the others (getGenoTypeMap().size())           */
+  uint64_t variant_objects;       /* sum of copies: code 1 -> 1, code 2 -> 2 ("Variant Count"); code-3 cells excluded ... */
+  uint64_t non_diploid_cells;     /* ... and counted here                                                  */
+  uint64_t unique_variants;       /* rows of the gene with >= 1 carrier ("Unique filter")                  */
+  uint64_t singleton_variants;    /* rows carried by exactly one genome (getSingletonVariants().size())    */
+  uint64_t singleton_genomes;     /* distinct genomes carrying such a row (getSingletonGenomes().size())   */
+  uint64_t top[5];                /* the five largest genotype classes, descending, 0-padded (getTopCounts<5>) */
+} kgx_gene_census;
+/* row_key: the hash of every row's HGVS (the reference's Utility::hash is a CRC-32; any 64-bit value is summed as it is).
+ * hash / counts may be NULL.  counts[gene][g] = { rows carried, of those with code 2, with code 3, singleton rows carried }.
+ * Run lists: run_begin[i] .. run_begin[i+1] = gene i's distinct hashes in ASCENDING order (std::map<size_t, ...> order, in which
+ * the reference sums HRel) with the number of genomes holding each.  run_hash == run_count == NULL: only census and run_begin
+ * are filled and run_begin[n_genes] is the capacity needed -- the sizing convention of kgx_genome_row_lists; a capacity below
+ * that: KGX_EINVAL.
+ * Scratch comes from the grow-only arena (kgx_release_scratch).  Genes are processed in batches when the census' buffers --
+ * 48 B per (gene, genome): hash, counts, the compacted and the sorted keys, the sort's second buffer -- would exceed a quarter of
+ * the device's free memory; batching never changes a result.  KGX_GENE_SMALL=b or b,s (read at kgx_init /
+ * kgx_reload_options) caps the genes per batch at b and sets the genes per workgroup slice to s (default b): the tests cross both
+ * boundaries at small sizes with it. */
+int kgx_gene_genotypes(kgx_pop* pop, const uint64_t* row_key /* host [n_variants] */,
+                       const uint32_t* member_rows, uint64_t n_members,
+                       const uint32_t* first_member, const uint32_t* n_rows, uint64_t n_genes,
+                       uint64_t* hash      /* host [n_genes][n_genomes] or NULL */,
+                       uint32_t* counts    /* host [n_genes][n_genomes][4] or NULL */,
+                       kgx_gene_census* census /* host [n_genes] */,
+                       uint64_t* run_begin /* host [n_genes + 1] */,
+                       uint64_t* run_hash, uint32_t* run_count /* host [capacity], or both NULL to size the call */,
+                       uint64_t capacity);
+/* Device time (HIP events) of the hashing kernel of the last call, summed over its batches (the slowest shard's).  Algorithmic
+ * bytes: member rows x ceil(G/4) + 8 B per member + 24 B per (gene, genome). */
+double kgx_gene_genotypes_last_ms(void);
+/* GenotypeAnalysis::Gini / HRel / IQV (_variant.cpp:499-628) of one gene's genotype distribution: run_count[n_runs] as
+ * kgx_gene_genotypes returns them (HRel is summed in the order given, the zero-variant term first) and the gene's
+ * zero_variant_genomes.  The reference's quirks are kept: the zero-variant genomes are one more category even when there are
+ * none; IQV divides its proportions by total x 100; without a genotype Gini and IQV are 1.0 and HRel 0.0.  Gini's sum of
+ * |f_i - f_j| is computed in integers from sorted counts (the same double below 2^53).  The CSV's "2-IQV" column is 2 - out[2].
+ * Host only, no device. */
+int kgx_genotype_statistics(const uint32_t* run_count, uint64_t n_runs, uint64_t zero_variant_genomes,
+                            double out[3] /* Gini, HRel, IQV */);
+
 /* ---- K4: VariantDBVariant::populationSummary (kgl_variant_db_variant.cpp:234-279). */
 int kgx_population_summary(kgx_pop* pop, uint64_t out[4]);
 

@@ -109,7 +109,16 @@ _SIGNATURES = {
     "kgx_unique_phased_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "kgx_offset_filter_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
                                            C.c_void_p]),
+    "kgx_gene_genotypes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "kgx_gene_genotypes_last_ms": (C.c_double, []),
+    "kgx_genotype_statistics": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
 }
+
+# kgx_gene_census (include/kgx.h), field for field
+GENE_CENSUS = np.dtype([("genomes", "<u8"), ("zero_variant_genomes", "<u8"), ("genotypes", "<u8"), ("variant_objects", "<u8"),
+                        ("non_diploid_cells", "<u8"), ("unique_variants", "<u8"), ("singleton_variants", "<u8"), ("singleton_genomes", "<u8"),
+                        ("top", "<u8", (5,))])
 
 
 def declared_symbols() -> list[str]:
@@ -470,6 +479,32 @@ class Population:
         check(lib().kgx_genome_row_lists(self._h, g0, g1, ptr(sel) if sel is not None else None, ptr(begin), ptr(rows), len(rows)))
         return begin, rows
 
+    def gene_genotypes(self, row_key, member_rows, first_member, n_rows, want_hash: bool = True, want_counts: bool = True):
+        """The gene genotype tables (kgx_gene_genotypes): gene i = member_rows[first_member[i] : + n_rows[i]], row_key[n_variants]
+        uint64.  Returns (census [n_genes] GENE_CENSUS, (run_begin [n_genes + 1] uint64, run_hash uint64, run_count uint32),
+        hash [n_genes][n_genomes] uint64 or None, counts [n_genes][n_genomes][4] uint32 or None).  Makes the sizing call itself."""
+        key = np.ascontiguousarray(row_key, dtype=np.uint64)
+        if key.shape != (self.n_variants,):
+            raise ValueError("row_key must be [n_variants]")
+        mr = np.ascontiguousarray(member_rows, dtype=np.uint32)
+        fm = np.ascontiguousarray(first_member, dtype=np.uint32)
+        nr = np.ascontiguousarray(n_rows, dtype=np.uint32)
+        if fm.shape != nr.shape or fm.ndim != 1:
+            raise ValueError("first_member and n_rows must be [n_genes]")
+        n_genes = len(fm)
+        census = np.zeros(n_genes, dtype=GENE_CENSUS)
+        begin = np.zeros(n_genes + 1, dtype=np.uint64)
+        hash_ = np.zeros((n_genes, self.n_genomes), dtype=np.uint64) if want_hash else None
+        counts = np.zeros((n_genes, self.n_genomes, 4), dtype=np.uint32) if want_counts else None
+        args = (self._h, ptr(key), ptr(mr), len(mr), ptr(fm), ptr(nr), n_genes)
+        check(lib().kgx_gene_genotypes(*args, None, None, ptr(census), ptr(begin), None, None, 0))
+        capacity = int(begin[-1])
+        run_hash = np.zeros(max(capacity, 1), dtype=np.uint64)
+        run_count = np.zeros(max(capacity, 1), dtype=np.uint32)
+        check(lib().kgx_gene_genotypes(*args, None if hash_ is None else ptr(hash_), None if counts is None else ptr(counts), ptr(census), ptr(begin),
+                                       ptr(run_hash), ptr(run_count), capacity))
+        return census, (begin, run_hash[:capacity], run_count[:capacity]), hash_, counts
+
     def load_phase_plane(self, both_phases: np.ndarray, v0: int = 0) -> None:
         """both_phases: [rows][n_genomes] booleans -- the genome's copies of the row's variant sit on both phases."""
         bits = np.packbits(np.ascontiguousarray(both_phases, dtype=np.uint8), axis=1, bitorder="little")
@@ -486,6 +521,20 @@ class Population:
         out = np.zeros(4, dtype=np.uint64)
         check(lib().kgx_population_summary(self._h, ptr(out)))
         return out
+
+
+def gene_genotypes_last_ms() -> float:
+    """Device time of the hashing kernel of the last gene_genotypes call (the slowest shard's)."""
+    return float(lib().kgx_gene_genotypes_last_ms())
+
+
+def genotype_statistics(run_count, zero: int) -> tuple[float, float, float]:
+    """(Gini, HRel, IQV) of a genotype distribution as GenotypeAnalysis computes them: run_count in std::map order (ascending
+    hash, as gene_genotypes returns it), zero = the genomes without a variant.  Host only."""
+    rc = np.ascontiguousarray(run_count, dtype=np.uint32)
+    out = np.zeros(3, dtype=np.float64)
+    check(lib().kgx_genotype_statistics(ptr(rc) if len(rc) else None, len(rc), int(zero), ptr(out)))
+    return float(out[0]), float(out[1]), float(out[2])
 
 
 def count_by_genome_last_ms() -> float:

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "kga_analysis_gpu_allele.h"
+#include "kga_analysis_gpu_gene.h"
 #include "kgx_flatten.h"
 #include "kgx_variant_sort.h"
 #include "kgx_vcf_io.h"
@@ -462,6 +463,43 @@ char* kgxh_variant_sort_file(const char* path, int flavour, const char* genome_i
                                  genome_id ? genome_id : "Reference", threads > 0 ? threads : 0, chunk_bytes ? static_cast<size_t>(chunk_bytes) : (size_t{64} << 20)))
     return nullptr;
   return dumpVariantSort(columns, what, splitNames(list), threads, t_begin);
+}
+
+// GpuGeneGenotypes over a population given as plain arrays: the HGVS of every row, the packed 2-bit rows (row_bytes =
+// ceil(n_genomes / 4) each) and the genes as row lists (gene i = member_rows[first_member[i] .. + gene_rows[i])) with the three
+// texts of their CSV line.  Needs a bound device (kgx_init); keep (may be null) is the genome mask.  Writes the reference's gene
+// file to csv_path; non-zero + message on failure.
+int kgxh_gene_genotypes_write(uint64_t n_genomes, uint64_t n_rows, const char* const* hgvs, const uint8_t* packed, const uint8_t* keep, uint64_t n_genes,
+                              const char* const* gene_ids, const uint64_t* coding_length, const char* const* gene_detail, const uint32_t* member_rows,
+                              const uint32_t* first_member, const uint32_t* gene_rows, const char* csv_path, char* error, size_t error_len) {
+  namespace g = kellerberrin::genome::analysis::gpu;
+  auto failed = [&](const std::string& message) {
+    if (error && error_len) { std::strncpy(error, message.c_str(), error_len - 1); error[error_len - 1] = 0; }
+    return 1;
+  };
+  if (!hgvs || !packed || !csv_path || (n_genes && (!gene_ids || !coding_length || !gene_detail || !first_member || !gene_rows))) return failed("null argument");
+  std::vector<g::VariantRow> rows(n_rows);
+  for (uint64_t r = 0; r < n_rows; ++r) rows[r].hgvs = hgvs[r];
+  std::vector<g::GeneRowList> genes(n_genes);
+  for (uint64_t i = 0; i < n_genes; ++i) {
+    genes[i].id = gene_ids[i];
+    genes[i].coding_length = coding_length[i];
+    genes[i].detail = gene_detail[i];
+    genes[i].rows.assign(member_rows + first_member[i], member_rows + first_member[i] + gene_rows[i]);
+  }
+  kgx_pop* pop = kgx_population_create(n_genomes, n_rows);
+  if (!pop) return failed(std::string("kgx_population_create: ") + kgx_last_error());
+  const uint64_t row_bytes = (n_genomes + 3) / 4;
+  int status = 0;
+  if (kgx_population_load_dosage2(pop, packed, row_bytes, 0, n_rows) != KGX_OK || (keep && kgx_population_set_genome_mask(pop, keep) != KGX_OK)) {
+    status = failed(std::string("loading the population: ") + kgx_last_error());
+  } else {
+    g::GpuGeneGenotypes analysis(rows, std::move(genes));
+    if (!analysis.analyze(pop)) status = failed(analysis.error());
+    else if (!analysis.writeGeneResults(csv_path)) status = failed(std::string("cannot write ") + csv_path);
+  }
+  kgx_population_destroy(pop);
+  return status;
 }
 
 }  // extern "C"
