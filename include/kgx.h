@@ -236,6 +236,17 @@ int kgx_unique_phased_counts(kgx_pop* pop, const uint8_t* bin_of_variant, uint32
 int kgx_genome_row_lists(kgx_pop* pop, uint64_t g0, uint64_t g1, const uint8_t* row_selected /* or NULL */, uint64_t* begin,
                          uint32_t* rows /* or NULL */, uint64_t capacity);
 
+/* A diagnostic, so that a test of a sweep's long pieces cannot quietly run short ones: how the most recent launch of one kind cut
+ * its work on the first shard's device.  out = { pieces launched, units in the longest piece, the kernel's own period in the same
+ * units } -- by-genome sweep (K3, the phase plane included): stretches of the selected-row list, list positions, the positions a
+ * lane's counters take between two flushes at this row width; compound offsets / offset filters (K8): group slices, groups, the
+ * rows a 4-bit field sum holds (15); row lists: row slices, rows, the rows of a tile (64).  The switches KGX_K3_PIECES,
+ * KGX_K8_SLICES and KGX_LIST_SLICES cap the first number; no switch changes the third.  Zeros before the first launch. */
+#define KGX_WORK_BY_GENOME 0
+#define KGX_WORK_OFFSETS   1
+#define KGX_WORK_ROW_LISTS 2
+int kgx_dosage_last_work(int which, uint64_t out[3]);
+
 /* ---- Gene genotype tables: the gene-variant analysis of the PfEMP package (kga_analytic/kga_PfEMP/kga_analysis_PfEMP_variant.{h,cpp};
  *      callers kga_analysis_PfEMP.cpp:100-103,136-144).  For every gene the reference walks every genome through std::map lookups
  *      and writes one CSV line (writeGeneResults, _variant.cpp:109-233).  All of that line follows from

@@ -113,6 +113,7 @@ _SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "kgx_gene_genotypes_last_ms": (C.c_double, []),
     "kgx_genotype_statistics": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "kgx_dosage_last_work": (C.c_int, [C.c_int, C.c_void_p]),
 }
 
 # kgx_gene_census (include/kgx.h), field for field
@@ -535,6 +536,17 @@ def genotype_statistics(run_count, zero: int) -> tuple[float, float, float]:
     out = np.zeros(3, dtype=np.float64)
     check(lib().kgx_genotype_statistics(ptr(rc) if len(rc) else None, len(rc), int(zero), ptr(out)))
     return float(out[0]), float(out[1]), float(out[2])
+
+
+DOSAGE_WORK = {"by_genome": 0, "offsets": 1, "row_lists": 2}
+
+
+def dosage_last_work(which: str) -> tuple[int, int, int]:
+    """(pieces launched, units in the longest piece, the kernel's own period) of the most recent by-genome sweep, compound
+    offsets / offset filters launch or row-list launch on the first shard's device (kgx.h: kgx_dosage_last_work)."""
+    out = np.zeros(3, dtype=np.uint64)
+    check(lib().kgx_dosage_last_work(DOSAGE_WORK[which], ptr(out)))
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 def count_by_genome_last_ms() -> float:

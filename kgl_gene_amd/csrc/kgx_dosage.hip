@@ -24,6 +24,20 @@ int require_runtime(std::shared_ptr<Runtime>& rt) {
   return KGX_OK;
 }
 
+// What kgx_dosage_last_work reports of the device's last launch of one kind.
+void note_work(Device& dev, int which, uint64_t pieces, uint64_t longest, uint64_t period) {
+  dev.last_dosage_work[which][0] = pieces;
+  dev.last_dosage_work[which][1] = longest;
+  dev.last_dosage_work[which][2] = period;
+}
+
+// A cap on a launch's number of pieces (KGX_K3_PIECES, KGX_K8_SLICES, KGX_LIST_SLICES): it only ever lowers the count, so
+// that a test reaches at a small size what a piece does at full size; unset or <= 0 = no cap.
+uint64_t capped(uint64_t count, const char* name) {
+  const int cap = env_int(name, 0);
+  return cap > 0 && count > static_cast<uint64_t>(cap) ? static_cast<uint64_t>(cap) : count;
+}
+
 // Lanes cooperating on one row: smallest power of two covering the row's 16-byte chunks, <= 64.
 int lanes_per_row(uint32_t chunks_per_row) {
   int w = 1;
@@ -226,7 +240,7 @@ int count_by_genome_shard(kgx_pop_shard& sh, const uint8_t* bin_of_variant, uint
   ScratchPlan plan;
   const size_t o_acc = plan.add(acc_words * sizeof(uint32_t)), o_out = plan.add((cells ? cells : 1) * 4 * sizeof(unsigned long long));
   const size_t o_nbin = plan.add(n_bins * sizeof(unsigned long long)), o_binoff = plan.add((n_bins + 1) * sizeof(unsigned long long));
-  const size_t o_bins = plan.add(identity ? 0 : V), o_index = plan.add(identity ? 0 : (V + 8) * sizeof(uint32_t));
+  const size_t o_bins = plan.add(identity ? 0 : V), o_index = plan.add(identity ? 0 : (V + kIndexPad) * sizeof(uint32_t));
   const size_t o_chunks = plan.add(identity ? 0 : static_cast<uint64_t>(n_chunks) * n_bins * sizeof(uint32_t)), o_work = plan.add(max_work * sizeof(GenomeWork));
   char* arena = nullptr;
   if (int arc = scratch_reserve(dev, plan.total, &arena)) return arc;
@@ -247,9 +261,9 @@ int count_by_genome_shard(kgx_pop_shard& sh, const uint8_t* bin_of_variant, uint
     try_hip(hipStreamSynchronize(st), KGX_EHIP, "sync");
   } else if (V > 0) {
     d_bins = reinterpret_cast<uint8_t*>(arena + o_bins);
-    d_index = reinterpret_cast<uint32_t*>(arena + o_index);                                       // + 8: whole 8-entry scalar fetches
+    d_index = reinterpret_cast<uint32_t*>(arena + o_index);                                       // + kIndexPad: whole 8-entry scalar fetches of a step's four waves
     d_chunks = reinterpret_cast<uint32_t*>(arena + o_chunks);
-    try_hip(hipMemsetAsync(d_index + V, 0, 8 * sizeof(uint32_t), st), KGX_EHIP, "memset(index pad)");
+    try_hip(hipMemsetAsync(d_index + V, 0, kIndexPad * sizeof(uint32_t), st), KGX_EHIP, "memset(index pad)");
     if (bin_edges) {
       // d_binoff is not read before k_bin_scan writes it: the edges borrow it on their way in
       static_assert(sizeof(double) == sizeof(unsigned long long), "edge buffer");
@@ -277,11 +291,13 @@ int count_by_genome_shard(kgx_pop_shard& sh, const uint8_t* bin_of_variant, uint
   }
   const uint64_t selected = bin_offset[n_bins];
   bool timed = false;
+  note_work(dev, KGX_WORK_BY_GENOME, 0, 0, by_genome_flush_period(W));
 
   if (rc == KGX_OK && selected > 0) {
-    const uint64_t gran = static_cast<uint64_t>(64 / W) * (kBlock / kWave) * 8;
+    const uint64_t gran = by_genome_step_positions(W);
     uint64_t pieces = target / n_cg;                          // stretches of the row list; each becomes n_cg items
     if (pieces < 1) pieces = 1;
+    pieces = capped(pieces, "KGX_K3_PIECES");
     uint64_t per_wg = (selected + pieces - 1) / pieces;
     per_wg = (per_wg + gran - 1) / gran * gran;
     if (per_wg < gran * 4) per_wg = gran * 4;
@@ -300,6 +316,7 @@ int count_by_genome_shard(kgx_pop_shard& sh, const uint8_t* bin_of_variant, uint
     try_hip(hipStreamSynchronize(st), KGX_EHIP, "sync");     // `work` is pageable host memory
     if (rc == KGX_OK) {
       const uint32_t n_work = static_cast<uint32_t>(work.size());
+      note_work(dev, KGX_WORK_BY_GENOME, n_work / n_cg, per_wg < selected ? per_wg : selected, by_genome_flush_period(W));
       try_hip(hipEventRecord(dev.by_genome_begin, st), KGX_EHIP, "hipEventRecord");
       (void)dispatch_by_genome(W, sh, source, shape, static_cast<const uint32_t*>(d_index), static_cast<const GenomeWork*>(d_work), n_work,
                                static_cast<const unsigned long long*>(d_binoff), n_bins, d_acc, static_cast<int*>(nullptr));
@@ -372,8 +389,10 @@ int compound_offsets_shard(kgx_pop_shard& sh, const std::vector<OffsetGroup>& gr
     uint64_t slices = (static_cast<uint64_t>(dev.compute_units) * 8 + gx - 1) / gx;
     if (slices > n_groups) slices = n_groups;
     if (slices > 65535) slices = 65535;
+    slices = capped(slices, "KGX_K8_SLICES");
     const uint64_t per_slice = (n_groups + slices - 1) / slices;
     const uint32_t gy = static_cast<uint32_t>((n_groups + per_slice - 1) / per_slice);
+    note_work(*sh.dev, KGX_WORK_OFFSETS, gy, per_slice, kOffsetFieldRows);
     if (hipMemsetAsync(d_acc, 0, cells * sizeof(unsigned long long), dev.stream) != hipSuccess ||
         hipMemcpyAsync(d_groups, groups.data(), n_groups * sizeof(OffsetGroup), hipMemcpyHostToDevice, dev.stream) != hipSuccess ||
         (d_list && hipMemcpyAsync(d_list, row_list.data(), row_list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, dev.stream) != hipSuccess)) {
@@ -418,8 +437,10 @@ int genome_row_lists_shard(kgx_pop_shard& sh, uint64_t g_lo, uint64_t g_hi, cons
   const uint64_t tiles = (V + kWave - 1) / kWave;
   if (slices > tiles) slices = tiles;
   if (slices > 65535) slices = 65535;
+  slices = capped(slices, "KGX_LIST_SLICES");
   const uint64_t rows_per_slice = (tiles + slices - 1) / slices * kWave;
   slices = (V + rows_per_slice - 1) / rows_per_slice;
+  note_work(dev, KGX_WORK_ROW_LISTS, slices, rows_per_slice < V ? rows_per_slice : V, kWave);
   uint8_t* d_sel = nullptr;
   uint32_t *d_counts = nullptr, *d_out = nullptr;
   unsigned long long *d_cursors = nullptr, *d_begin = nullptr, *d_totals = nullptr;
@@ -1129,6 +1150,13 @@ double kgx_count_by_genome_last_ms(void) {
   if (rt)
     for (const auto& dev : rt->devs) { const double ms = dev->last_by_genome_ms.load(); worst = ms > worst ? ms : worst; }
   return worst;
+}
+
+int kgx_dosage_last_work(int which, uint64_t out[3]) {
+  if (which < 0 || which > KGX_WORK_ROW_LISTS || !out) return fail(KGX_EINVAL, "kgx_dosage_last_work: which %d outside [0, %d] or null output", which, KGX_WORK_ROW_LISTS);
+  const auto rt = current_runtime();
+  for (int i = 0; i < 3; ++i) out[i] = rt && !rt->devs.empty() ? rt->devs[0]->last_dosage_work[which][i].load() : 0;
+  return KGX_OK;
 }
 
 int kgx_compound_offsets(kgx_pop* pop, const uint32_t* first_row, const uint32_t* n_rows, const uint32_t* bin,

@@ -45,6 +45,8 @@ struct Device {
   std::atomic<double> last_sweep_ms{0.0}, last_kernel_ms{0.0}, last_moments_ms{0.0}, last_search_ms{0.0};
   std::atomic<int> last_evaluations{0};                    // objective evaluations of the last Loglikelihood call here
   std::atomic<int> last_path{0};                           // KGX_PATH_*: what the last kgx_inbreed call here ran on
+  // kgx_dosage_last_work: [KGX_WORK_*] = { pieces launched, units in the longest piece, the kernel's period } of the last such launch here
+  std::atomic<uint64_t> last_dosage_work[3][3] = {};
   char* scratch = nullptr;                                 // grow-only arena for kgx_inbreed's per-call buffers
   size_t scratch_bytes = 0;
   char* compact[2] = {nullptr, nullptr};                   // ping-pong buffers of the Loglikelihood search's compaction levels

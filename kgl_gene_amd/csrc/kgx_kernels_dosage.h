@@ -9,6 +9,7 @@
 #define KGX_KERNELS_DOSAGE_H
 
 #include "kgx_kernels_common.h"
+#include "kgx_sliced_counters.h"
 #include "kgx_synth.h"
 
 namespace kgx {
@@ -182,60 +183,16 @@ struct GenomeWork {
 };
 constexpr int kAccCounters = 192;            // per (bin, column group): 128 stream counters + 64 non-diploid ones, x kLdsStride lanes
 
-constexpr int kHiPlanes = 8;                 // weights 16 .. 2048
-constexpr int kBlocksPerFlush = 510;         // blocks of 8 rows: 510*8 + 15 < 16 * 2^kHiPlanes
 constexpr int kLdsStride = 64;               // lanes per counter row in LDS
+// csa, SlicedCounters, kHiPlanes, kBlocksPerFlush: kgx_sliced_counters.h (host-checkable)
 
-__device__ __forceinline__ void csa(uint32_t& carry, uint32_t& sum, uint32_t a, uint32_t b, uint32_t c) {
-  const uint32_t u = a ^ b;
-  carry = (a & b) | (u & c);
-  sum = u ^ c;
-}
-
-template <int NW>
-struct SlicedCounters {
-  // bit planes of weight 1, 2, 4, 8 and 16 << p; pending = the weight-8 carry of an odd block, waiting for its partner
-  uint32_t ones[NW], twos[NW], fours[NW], eights[NW], hi[NW][kHiPlanes], pending[NW];
-  __device__ __forceinline__ void clear() {
-#pragma unroll
-    for (int i = 0; i < NW; ++i) {
-      ones[i] = twos[i] = fours[i] = eights[i] = pending[i] = 0;
-#pragma unroll
-      for (int p = 0; p < kHiPlanes; ++p) hi[i][p] = 0;
-    }
-  }
-  // Fold 8 input words of stream-word i; returns the carry of weight 8.
-  __device__ __forceinline__ uint32_t add8(int i, const uint32_t x[8]) {
-    uint32_t t2a, t2b, f4a, f4b, e8;
-    csa(t2a, ones[i], ones[i], x[0], x[1]);
-    csa(t2b, ones[i], ones[i], x[2], x[3]);
-    csa(f4a, twos[i], twos[i], t2a, t2b);
-    csa(t2a, ones[i], ones[i], x[4], x[5]);
-    csa(t2b, ones[i], ones[i], x[6], x[7]);
-    csa(f4b, twos[i], twos[i], t2a, t2b);
-    csa(e8, fours[i], fours[i], f4a, f4b);
-    return e8;
-  }
-  // Two weight-8 carries (of two blocks of 8 rows) into the weight-8 plane; its carry ripples through the planes above --
-  // once per 16 rows instead of once per 8.
-  __device__ __forceinline__ void add_eights(int i, uint32_t a, uint32_t b) {
-    uint32_t c16;
-    csa(c16, eights[i], eights[i], a, b);
-#pragma unroll
-    for (int p = 0; p < kHiPlanes; ++p) {
-      const uint32_t t = hi[i][p] & c16;
-      hi[i][p] ^= c16;
-      c16 = t;
-    }
-  }
-  // Integer count of bit position b of stream-word i.
-  __device__ __forceinline__ uint32_t value(int i, int b) const {
-    uint32_t v = ((ones[i] >> b) & 1u) | (((twos[i] >> b) & 1u) << 1) | (((fours[i] >> b) & 1u) << 2) | (((eights[i] >> b) & 1u) << 3);
-#pragma unroll
-    for (int p = 0; p < kHiPlanes; ++p) v |= ((hi[i][p] >> b) & 1u) << (4 + p);
-    return v;
-  }
-};
+// Selected-row list positions a workgroup walks per step of by_genome_pass at W lanes per row (8 rows per lane), and
+// between two flushes of the lanes' counters: the flush period kgx_dosage_last_work reports.
+constexpr uint64_t by_genome_step_positions(int W) { return static_cast<uint64_t>(kWave / W) * (kBlock / kWave) * 8; }
+constexpr uint64_t by_genome_flush_period(int W) { return by_genome_step_positions(W) * kBlocksPerFlush; }
+// row_index is padded by this many entries: the scalar fetch of the last wave of a step that starts one position before
+// the end of the list reads whole 8-entry groups up to kIndexPad - 1 positions past it (values not used).
+constexpr uint32_t kIndexPad = (kBlock / kWave) * 8;
 
 // MODE 0: stream words are the 4 chunk dwords (bit 2j = code&1, bit 2j+1 = code&2 of genome j).
 // MODE 1: two words of (code==3) indicators: word0 = t(dw0) | t(dw1)<<1, word1 = t(dw2) | t(dw3)<<1.
@@ -276,7 +233,7 @@ __device__ __forceinline__ void by_genome_pass(const kgx_v4u* __restrict__ rows,
   // Gathered rows (the bins) with one row per wave-step slot (W == 64): a wave takes 8 CONSECUTIVE list positions per
   // step, so their row numbers are one wave-uniform 32-byte scalar load -- on the scalar memory counter, where it does
   // not queue behind the row loads already in flight as a per-lane index load would (vector memory returns in order).
-  // row_index is padded by 8 entries past the list.
+  // row_index is padded by kIndexPad entries past the list: the four waves of the last step fetch up to there.
   const bool scalar_index = (W == kWave) && row_index != nullptr;
   const uint32_t wave_slot = __builtin_amdgcn_readfirstlane(slot);
   for (uint64_t p0 = wk.begin + slot; p0 - slot < wk.end; p0 += static_cast<uint64_t>(kRowSlots) * 8) {
@@ -558,6 +515,7 @@ struct OffsetGroup {
   uint32_t bin;        // output bin (contig index)
   uint32_t pad;
 };
+constexpr uint32_t kOffsetFieldRows = 15;    // rows a 4-bit field sum holds before it is drained
 
 __global__ void __launch_bounds__(kBlock)
 k_compound_offsets(const uint32_t* __restrict__ rows, uint64_t dwords_per_row, uint64_t n_genomes,
@@ -596,7 +554,7 @@ k_compound_offsets(const uint32_t* __restrict__ rows, uint64_t dwords_per_row, u
     // rows.  A wider group (the reference has no cap: kga_analysis_PfEMP_heterozygous.cpp:61-105) is walked 15 rows at a
     // time, the fields drained into per-genome counts in between.
     uint32_t present_e = 0, present_o = 0, single_e = 0, single_o = 0, ge2 = 0;
-    const bool wide = grp.n_rows > 15;
+    const bool wide = grp.n_rows > kOffsetFieldRows;
     uint32_t np_wide[16], ns_wide[16];
     if (wide) {
 #pragma unroll
@@ -612,7 +570,7 @@ k_compound_offsets(const uint32_t* __restrict__ rows, uint64_t dwords_per_row, u
       single_e += single & 0x11111111u;
       single_o += (single >> 2) & 0x11111111u;
       ge2 |= hi;
-      if (wide && (r % 15 == 14 || r + 1 == grp.n_rows)) {
+      if (wide && (r % kOffsetFieldRows == kOffsetFieldRows - 1 || r + 1 == grp.n_rows)) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
           np_wide[j] += ((j & 1) ? present_o : present_e) >> (4 * (j >> 1)) & 0xFu;
@@ -683,7 +641,7 @@ k_offset_filters(const uint32_t* __restrict__ rows, uint64_t dwords_per_row, uin
     // per-genome row counts in 4-bit fields, even and odd genomes apart: good for 15 rows; a wider group is walked 15 rows
     // at a time, the fields drained into per-genome counts in between (as in k_compound_offsets)
     uint32_t present_e = 0, present_o = 0, single_e = 0, single_o = 0, twice_e = 0, twice_o = 0, more = 0;
-    const bool wide = grp.n_rows > 15;
+    const bool wide = grp.n_rows > kOffsetFieldRows;
     uint32_t np_wide[16], ns_wide[16], n2_wide[16];
     if (wide) {
 #pragma unroll
@@ -701,7 +659,7 @@ k_offset_filters(const uint32_t* __restrict__ rows, uint64_t dwords_per_row, uin
       twice_e += twice & 0x11111111u;
       twice_o += (twice >> 2) & 0x11111111u;
       more |= lo & hi;
-      if (wide && (r % 15 == 14 || r + 1 == grp.n_rows)) {
+      if (wide && (r % kOffsetFieldRows == kOffsetFieldRows - 1 || r + 1 == grp.n_rows)) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
           const int shift = 4 * (j >> 1);
