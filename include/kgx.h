@@ -466,6 +466,41 @@ int kgx_inbreed_last_path(void);
 int kgx_inbreed_objective(kgx_gt8* gt, uint64_t g0, uint64_t g1, const uint32_t* locus_index, uint64_t n_selected,
                           const double* minor_af, uint32_t amax, int phased, const double* at, int by_passes, double* value);
 
+/* ---- allele census of the genotype matrix by genome group: the matrix's own AC / AN, which the reference reads from the INFO
+ *      fields of a second VCF (AFR_AF .. AF, kgl_variant_db_freq.h:84-96) -- for 1000-Genomes-style data the counts of exactly the
+ *      genomes that sit in the matrix, per super-population.
+ * Per selected locus and genome group, what the genomes of the group carry there.
+ * group_of_genome: host [n_genomes], a group in [0, n_groups) or 0xFF = in no group; any other value: KGX_EINVAL.
+ * n_groups in 1..32, amax in 1..14. locus_index: ascending rows of the matrix, host, NULL = 0..n_selected-1 (as kgx_inbreed).
+ * out: host [n_selected][n_groups][3 + 2*amax] uint32:
+ *   [0] reference_cells   cells equal to 0x00
+ *   [1] unknown_copies    copies of an alt the call cannot name: index 15, or an index in (amax, 14]
+ *   [2] crowded_cells     cells equal to 0xFF (three or more variants): no copies counted
+ *   [3 + 2*(a-1)] single_a   cells holding exactly ONE copy of alt a (a = 1..amax)
+ *   [4 + 2*(a-1)] double_a   cells holding TWO copies of alt a
+ * Copies of a cell (lo, hi) != 0xFF: hi == 0: lo once; lo == 0 && hi != 0: hi TWICE (the repeated-record pair, above);
+ * otherwise lo once and hi once (lo == hi: that alt twice). AC_a = single_a + 2*double_a; AN = 2 * genomes of the group
+ * (missing == reference-homozygous).
+ * A selected locus that has a wide row (kgx_gt8_set_wide_rows) is refused with KGX_EINVAL.  n_selected == 0 writes nothing.
+ * Works over any binding: every shard counts its own genomes on its device (ONE pass over the matrix bytes whatever n_groups
+ * and amax are: the counts are an exact int8 product on the matrix cores), the shards' counts are summed by the
+ * exchange step of the allele-count sweep; the result does not depend on the binding, and the same bits come out on every run.
+ * The device result comes from the grow-only arena (kgx_release_scratch); loci are processed in batches when its
+ * 4*(3+2*amax)*n_groups*n_selected bytes would exceed a quarter of the free memory, and KGX_CENSUS_LOCI=n (read at kgx_init /
+ * kgx_reload_options; unset or <= 0: no effect) caps the loci per batch.  Batching never changes a result. */
+int kgx_gt8_allele_census(kgx_gt8* gt, const uint8_t* group_of_genome, uint32_t n_groups,
+                          const uint32_t* locus_index, uint64_t n_selected, uint32_t amax, uint32_t* out);
+/* Kernel time (HIP events, slowest shard, summed over batches) and number of locus batches of the last call.  Algorithmic bytes:
+ * n_selected*G + G + 4*(3+2*amax)*n_groups*n_selected. */
+int kgx_gt8_allele_census_last(double* kernel_ms, uint64_t* batches);
+/* Host only, no device (like kgx_genotype_statistics): minor_af[l][a-1] = (double)(float)((double)AC / (double)AN)
+ * over the POOLED groups pool[0..n_pool) (one group, or several for "ALL"); group_genomes[n_groups] = genomes per group.
+ * n_alt: [n_loci] or NULL (= amax); columns >= n_alt[l] are NaN; AN == 0: the whole row NaN. AC == 0 gives 0.0, not NaN
+ * (an alt with INFO AF = 0 is in the AlleleFreqVector). unknown_copies never enter.  The rows are what kgx_inbreed takes. */
+int kgx_census_allele_frequencies(const uint32_t* census, uint64_t n_loci, uint32_t n_groups, uint32_t amax,
+                                  const uint64_t* group_genomes, const uint32_t* pool, uint32_t n_pool,
+                                  const uint8_t* n_alt, double* minor_af /* [n_loci][amax] */);
+
 /* Synthetic multi-allelic SNP+indel population (BASELINE.json configs[4]) written straight into
  * the matrix: 1/2/3 alts (70/20/10 %), 15 % of alts are indels, AFs rescaled to sum <= 0.6, genotypes drawn from
  * the reference's class probabilities at F = -0.5 + 0.01*((genome_base+g) % 101).  af_table (host, may be NULL)

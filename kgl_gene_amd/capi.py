@@ -114,6 +114,10 @@ _SIGNATURES = {
     "kgx_gene_genotypes_last_ms": (C.c_double, []),
     "kgx_genotype_statistics": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "kgx_dosage_last_work": (C.c_int, [C.c_int, C.c_void_p]),
+    "kgx_gt8_allele_census": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "kgx_gt8_allele_census_last": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kgx_census_allele_frequencies": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                C.c_void_p]),
 }
 
 # kgx_gene_census (include/kgx.h), field for field
@@ -659,6 +663,20 @@ class GenotypeMatrix:
             raise ValueError("cells must be [n_wide][n_genomes]")
         check(lib().kgx_gt8_set_wide_rows(self._h, len(rows), ptr(rows), ptr(c), self.n_genomes))
 
+    def allele_census(self, group_of_genome, n_groups: int, amax: int, locus_index=None, n_selected: int | None = None) -> np.ndarray:
+        """The allele census by genome group (kgx_gt8_allele_census): group_of_genome uint8 [n_genomes], a group or 0xFF.
+        Returns uint32 [n_selected][n_groups][3 + 2 * amax] = reference_cells, unknown_copies, crowded_cells, then
+        single_a, double_a for a = 1..amax."""
+        groups = np.ascontiguousarray(group_of_genome, dtype=np.uint8)
+        if groups.shape != (self.n_genomes,):
+            raise ValueError("group_of_genome must hold one group per genome")
+        idx = None if locus_index is None else np.ascontiguousarray(locus_index, dtype=np.uint32)
+        if n_selected is None:
+            n_selected = self.n_loci if idx is None else len(idx)
+        out = np.zeros((int(n_selected), int(n_groups), 3 + 2 * int(amax)), dtype=np.uint32)
+        check(lib().kgx_gt8_allele_census(self._h, ptr(groups), int(n_groups), None if idx is None else ptr(idx), int(n_selected), int(amax), ptr(out)))
+        return out
+
     def inbreed_batch(self, tasks, algorithm: str, phased: bool) -> list:
         """Many inbreed() calls in one (kgx_inbreed_batch): tasks = dicts with minor_af [n_selected][amax] and optionally
         locus_index, g0, g1, start -- all with the same amax.  Returns the tasks' result arrays in order."""
@@ -710,6 +728,33 @@ class GenotypeMatrix:
         check(lib().kgx_inbreed(self._h, g0, g1, None, n_selected, C.c_void_p(minor_af_dev), amax, int(bool(phased)), ALGORITHMS[algorithm],
                                 None if st is None else ptr(st), ptr(out)))
         return out
+
+
+def allele_census_last() -> tuple[float, int]:
+    """(kernel ms, locus batches) of the last allele_census call: HIP events, the slowest shard's, summed over the batches."""
+    ms, batches = C.c_double(0.0), C.c_uint64(0)
+    check(lib().kgx_gt8_allele_census_last(C.byref(ms), C.byref(batches)))
+    return float(ms.value), int(batches.value)
+
+
+def census_allele_frequencies(census, group_genomes, pool, n_alt=None) -> np.ndarray:
+    """kgx_census_allele_frequencies: the census [n_loci][n_groups][3 + 2 * amax] as minor_af [n_loci][amax] =
+    float64(float32(AC / AN)) over the pooled groups `pool`; group_genomes [n_groups] = genomes per group; n_alt [n_loci] or
+    None (= amax).  Host only."""
+    c = np.ascontiguousarray(census, dtype=np.uint32)
+    n_loci, n_groups, kinds = c.shape
+    amax = (kinds - 3) // 2
+    sizes = np.ascontiguousarray(group_genomes, dtype=np.uint64)
+    if sizes.shape != (n_groups,):
+        raise ValueError("group_genomes must hold one count per group")
+    members = np.ascontiguousarray(pool, dtype=np.uint32)
+    alts = None if n_alt is None else np.ascontiguousarray(n_alt, dtype=np.uint8)
+    if alts is not None and alts.shape != (n_loci,):
+        raise ValueError("n_alt must hold one count per locus")
+    out = np.zeros((n_loci, amax), dtype=np.float64)
+    check(lib().kgx_census_allele_frequencies(ptr(c), n_loci, n_groups, amax, ptr(sizes), ptr(members) if len(members) else None, len(members),
+                                              None if alts is None else ptr(alts), ptr(out)))
+    return out
 
 
 def reference_starts(algorithm: str, seed: int, n: int, first_stream: int = 0) -> np.ndarray:

@@ -9,6 +9,7 @@
 #include <functional>
 #include <iomanip>
 #include <limits>
+#include <numeric>
 #include <sstream>
 #include <unordered_map>
 
@@ -203,6 +204,14 @@ bool kga::GpuInbreedAnalysis::initializeAnalysis(const std::string& work_directo
       if (auto v = parameter_map.getSize("StartSeed")) start_seed_ = v.value().front();
       if (auto v = parameter_map.getSize("WindowBatch")) window_batch_ = std::max<size_t>(1, v.value().front());
       if (auto v = parameter_map.getString("StartPoints")) start_midpoints_ = v.value().front() == "Midpoint";
+      if (auto v = parameter_map.getString("FrequencySource")) {
+        const std::string& source = v.value().front();
+        if (source != "Reference" && source != "Population") {
+          ExecEnv::log().error("GpuInbreedAnalysis::initializeAnalysis; FrequencySource: {} is neither Reference nor Population", source);
+          return false;
+        }
+        population_frequencies_ = source == "Population";
+      }
     }
   for (const auto& parameter : extractParameters(named_parameters)) {
     GpuParamOutput out;
@@ -557,6 +566,7 @@ bool kga::GpuInbreedAnalysis::populationInbreeding(GpuParamOutput& param_output)
     ExecEnv::log().warn("GpuInbreedAnalysis; {} reference offsets hold more than 14 SNP alts (the widest {}): their cells are kept as 16-bit rows and the "
                         "windows that sample them are swept on their own", n_wide, reference.max_alts);
   }
+  if (population_frequencies_ && !populationFrequencies(dev.handle, reference, amax, range_begin, range_end, device_genomes)) return false;
 
   // The window loop of InbreedingAnalysis::populationInbreeding (_diploid.cpp:43-75).  Windows are independent once sampled --
   // a window's bounds follow from the reference contig alone, its super populations differ in their frequency rows and
@@ -669,6 +679,56 @@ bool kga::GpuInbreedAnalysis::populationInbreeding(GpuParamOutput& param_output)
     current.swap(ahead);
   }
   return !start_failed;
+}
+
+bool kga::GpuInbreedAnalysis::populationFrequencies(kgx_gt8* matrix, GpuReferenceContig& reference, uint32_t amax, const std::vector<uint64_t>& range_begin,
+                                                    const std::vector<uint64_t>& range_end, uint64_t device_genomes) const {
+  const uint32_t n_groups = static_cast<uint32_t>(range_begin.size());          // a group per super population slot (ALL's own is empty)
+  std::vector<uint8_t> group_of_genome(device_genomes, 0xFF);                   // the padding between two groups: in no group
+  std::vector<uint64_t> group_genomes(n_groups, 0);
+  std::vector<uint32_t> everybody;
+  for (uint32_t sp = 0; sp < n_groups; ++sp) {
+    std::fill(group_of_genome.begin() + static_cast<std::ptrdiff_t>(range_begin[sp]), group_of_genome.begin() + static_cast<std::ptrdiff_t>(range_end[sp]),
+              static_cast<uint8_t>(sp));
+    group_genomes[sp] = range_end[sp] - range_begin[sp];
+    everybody.push_back(sp);
+  }
+  // offsets with more than 14 alts keep the reference's values: their cells are not in the matrix bytes
+  std::vector<uint32_t> narrow;
+  std::vector<uint8_t> n_alt;
+  for (size_t l = 0; l < reference.loci.size(); ++l)
+    if (!reference.isWide(l)) {
+      narrow.push_back(static_cast<uint32_t>(l));
+      n_alt.push_back(static_cast<uint8_t>(reference.loci[l].alts.size()));
+    }
+  const size_t n_wide = reference.loci.size() - narrow.size();
+  if (n_wide) ExecEnv::log().warn("GpuInbreedAnalysis; FrequencySource Population: {} reference offsets hold more than 14 SNP alts and keep the reference file's frequencies", n_wide);
+  if (narrow.empty()) return true;
+  const uint32_t kinds = 3 + 2 * amax;
+  std::vector<uint32_t> census(narrow.size() * n_groups * kinds);
+  if (kgx_gt8_allele_census(matrix, group_of_genome.data(), n_groups, n_wide ? narrow.data() : nullptr, narrow.size(), amax, census.data()) != KGX_OK) {
+    ExecEnv::log().error("GpuInbreedAnalysis; allele census of the population failed: {}", kgx_last_error());
+    return false;
+  }
+  const auto& super_pops = FrequencyDatabaseRead::superPopulations();
+  const size_t all_slot = static_cast<size_t>(std::find(super_pops.begin(), super_pops.end(), std::string(FrequencyDatabaseRead::SUPER_POP_ALL_)) - super_pops.begin());
+  std::vector<double> minor_af(narrow.size() * amax);
+  for (uint32_t sp = 0; sp < n_groups; ++sp) {
+    const bool all = sp == all_slot;
+    if (!all && group_genomes[sp] == 0) continue;                              // no genome, no task: the reference's values stay
+    if (kgx_census_allele_frequencies(census.data(), narrow.size(), n_groups, amax, group_genomes.data(), all ? everybody.data() : &sp, all ? n_groups : 1u,
+                                      n_alt.data(), minor_af.data()) != KGX_OK) {
+      ExecEnv::log().error("GpuInbreedAnalysis; allele frequencies of the population failed: {}", kgx_last_error());
+      return false;
+    }
+    for (size_t i = 0; i < narrow.size(); ++i) {
+      auto& alts = reference.loci[narrow[i]].alts;
+      for (size_t a = 0; a < alts.size(); ++a) alts[a].af[sp] = minor_af[i * amax + a];
+    }
+  }
+  ExecEnv::log().info("GpuInbreedAnalysis; FrequencySource Population: allele frequencies of {} offsets from the population's own {} genomes", narrow.size(),
+                      std::accumulate(group_genomes.begin(), group_genomes.end(), uint64_t{0}));
+  return true;
 }
 
 std::vector<double> kga::GpuInbreedAnalysis::startPoints(int algorithm, const std::vector<uint64_t>& streams) const {

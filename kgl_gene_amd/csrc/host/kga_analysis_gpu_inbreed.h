@@ -18,6 +18,8 @@
 #endif
 #include "kgx_flatten.h"
 
+struct kgx_gt8;   // include/kgx.h
+
 namespace kellerberrin::genome::analysis {
 
 // LociiVectorArguments + InbreedingParameters (kga_analysis_inbreed_args.h:69-160), defaults included.
@@ -126,6 +128,10 @@ class GpuInbreedAnalysis : public VirtualAnalysis {
   [[nodiscard]] bool haveDiploid() const { return diploid_population_ != nullptr || !diploid_vcf_.empty(); }
   // SyntheticAnalysis::syntheticInbreeding (kga_analysis_inbreed_synthetic.cpp:17-138)
   bool syntheticInbreeding(GpuParamOutput& param_output);
+  // FrequencySource = Population: af[sp] of every alt of every offset that fits a matrix byte, from the matrix on the device; the
+  // genomes of super population sp are the device columns [range_begin[sp], range_end[sp]).
+  bool populationFrequencies(kgx_gt8* matrix, GpuReferenceContig& reference, uint32_t amax, const std::vector<uint64_t>& range_begin,
+                             const std::vector<uint64_t>& range_end, uint64_t device_genomes) const;
 
  public:
   // InbreedSynthetic::generateSyntheticGenomeId / generateInbreeding (kga_analysis_inbreed_syngen.cpp:202-275)
@@ -143,6 +149,11 @@ class GpuInbreedAnalysis : public VirtualAnalysis {
   // reference's start intervals (0.25 / 0.0) -- a deterministic mode the reference does not have.
   uint64_t start_seed_{0};
   bool start_midpoints_{false};
+  // Parameter "FrequencySource": "Reference" (default) reads every allele frequency from the reference file's INFO fields, as the
+  // reference does; "Population" replaces them by the diploid population's own AC / AN per super population (and over all its
+  // genomes for ALL): ONE kgx_gt8_allele_census call over the matrix once it is on the device, kgx_census_allele_frequencies per
+  // super population.  Sampling, windows and writers read the same fields either way.  The synthetic self-check ignores it.
+  bool population_frequencies_{false};
   size_t window_batch_{16};                       // parameter WindowBatch: windows sampled ahead and handed to the device together (kgx_inbreed_batch)
   mutable std::array<std::vector<double>, 2> seeded_starts_;    // [HallME, Loglikelihood][stream]: drawn once under a StartSeed
   // The start points of n tasks, the first of which is the first_stream-th enqueued; empty = midpoints (or not iterative).

@@ -1155,6 +1155,7 @@ int kgx_gt8_set_wide_rows(kgx_gt8* h, uint64_t n_wide, const uint32_t* locus, co
       wide_of_row.assign(h->n_loci, 0xFFFFFFFFu);
       for (uint64_t i = 0; i < n_wide; ++i) wide_of_row[locus[i]] = static_cast<uint32_t>(i);
     }
+    h->wide_loci.assign(locus, locus + n_wide);
     for (auto& sh : h->shards) {
       if (int rc = use_device(*sh.dev)) return rc;
       KGX_HIP(hipStreamSynchronize(sh.dev->stream));

@@ -206,6 +206,7 @@ struct kgx_gt8 {
   uint64_t n_genomes = 0;
   uint64_t n_loci = 0;
   std::vector<kgx_gt8_shard> shards;
+  std::vector<uint32_t> wide_loci;   // the rows that have a wide row (kgx_gt8_set_wide_rows), ascending: what the allele census refuses
 };
 
 #define KGX_HIP(call)                                                                             \
