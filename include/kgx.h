@@ -309,6 +309,44 @@ double kgx_gene_genotypes_last_ms(void);
 int kgx_genotype_statistics(const uint32_t* run_count, uint64_t n_runs, uint64_t zero_variant_genomes,
                             double out[3] /* Gini, HRel, IQV */);
 
+/* ---- Pairwise joint genotype counts between genomes: what a sample x sample distance needs from the population itself.  The
+ *      reference READS such a matrix from a resource file (Pf7GeneticDistanceResource, kga_analysis_PfEMP_distance.cpp); a cohort
+ *      without that file had none.
+ * Kinds: H = code 1 (heterozygous), M = code 2 (minor homozygous), O = code 3 (non-diploid, which the reference does not count).
+ * For every unordered pair a <= b of genomes of the WHOLE population nine words at pair index a*G - a*(a-1)/2 + (b - a):
+ * word 3*p + q = the listed rows in which a has kind p and b has kind q, p and q in the order H, M, O.  The diagonal pair (a, a)
+ * holds the genome's own counts in words 0, 4 and 8 and zero elsewhere; the counts involving code 0 are not stored -- they follow
+ * from the diagonals and n_rows.
+ * rows: host [n_rows], any order, need not be adjacent, a row listed twice counts twice; NULL = rows 0 .. n_rows-1.  A row >=
+ * n_variants: KGX_EINVAL.  n_rows == 0 writes zeros.  Counts are exact (int8 -> int32 products on the matrix cores, DESIGN.md 12;
+ * the accumulators wrap like the uint32 they are stored as: n_rows < 2^32).  Honours the genome mask: a genome left out reads as
+ * code 0 everywhere -- all its words are zero, its own diagonal included (as K3 / K8 report masked genomes).
+ * Works over any binding: every shard turns the listed rows of its genomes into a genome-major panel on its device, the panels are
+ * copied behind one another on the FIRST slot's device and the product runs there; the result does not depend on the binding.
+ * The table (36*G*(G+1)/2 bytes) and one panel batch come from the grow-only arena (kgx_release_scratch): rows are processed in
+ * batches when the panel (n_rows*G/4 bytes) would exceed a quarter of (free + arena) on a device; a table that does not fit
+ * beside one 64-row panel: KGX_ENOMEM.  KGX_PAIRS_ROWS=n (read at kgx_init / kgx_reload_options; unset or <= 0: no effect) caps
+ * the rows per batch.  Batching never changes a result. */
+int kgx_pair_counts(kgx_pop* pop, const uint32_t* rows /* host [n_rows], or NULL = rows 0..n_rows-1 */,
+                    uint64_t n_rows, uint32_t* out /* host [G(G+1)/2][9] */);
+/* Of the last call: device time (HIP events, summed over the row batches) of the product kernel, the number of row batches, and
+ * into how many slices the rows of a batch were split over the grid (1 = not split; more where there are fewer 64-genome tile
+ * pairs than two workgroups per compute unit -- the slices then add into a zeroed table).  Multiply-accumulates of the product:
+ * 9 * G(G+1)/2 * n_rows. */
+int kgx_pair_counts_last(double* kernel_ms, uint64_t* row_batches, uint64_t* row_splits);
+/* ... and the device time of the panel kernels on the first slot's stream (the copies of other devices' panels not included). */
+double kgx_pair_counts_last_panel_ms(void);
+/* Distances from those counts.  Host only, no device (like kgx_census_allele_frequencies).  These are THE LIBRARY'S definitions
+ * over the listed rows -- not a claim to reproduce any published matrix file.  With H_a, M_a, O_a from the diagonal of a and
+ * n[p][q] the pair's words: jointly called rows N = n_rows - O_a - O_b + n[O][O]; X_a = (H_a - n[H][O]) + 2*(M_a - n[M][O]),
+ * X_b = (H_b - n[O][H]) + 2*(M_b - n[O][M]) (the dosage sums over the jointly called rows).
+ *   kind 0, IBS distance = mean |x_a - x_b| / 2:  T = X_a + X_b - 2*(n[H][H] + n[H][M] + n[M][H] + 2*n[M][M]);  out = T / (2 N)
+ *   kind 1, within-sample-frequency distance = mean of f_a (1 - f_b) + f_b (1 - f_a), f = x / 2:
+ *                                                  S = X_a + X_b - (n[H][H] + 2*n[H][M] + 2*n[M][H] + 4*n[M][M]);  out = S / (2 N)
+ * Each value is ONE IEEE double division of two exactly representable integers; N == 0 gives NaN; any other kind: KGX_EINVAL. */
+int kgx_pair_distances(const uint32_t* counts /* [G(G+1)/2][9] */, uint64_t n_genomes, uint64_t n_rows,
+                       int kind, double* out /* [G(G+1)/2] */);   /* host only */
+
 /* ---- K4: VariantDBVariant::populationSummary (kgl_variant_db_variant.cpp:234-279). */
 int kgx_population_summary(kgx_pop* pop, uint64_t out[4]);
 

@@ -118,6 +118,10 @@ _SIGNATURES = {
     "kgx_gt8_allele_census_last": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kgx_census_allele_frequencies": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                 C.c_void_p]),
+    "kgx_pair_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "kgx_pair_counts_last": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kgx_pair_counts_last_panel_ms": (C.c_double, []),
+    "kgx_pair_distances": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]),
 }
 
 # kgx_gene_census (include/kgx.h), field for field
@@ -510,6 +514,17 @@ class Population:
                                        ptr(run_hash), ptr(run_count), capacity))
         return census, (begin, run_hash[:capacity], run_count[:capacity]), hash_, counts
 
+    def pair_counts(self, rows=None, n_rows: int | None = None) -> np.ndarray:
+        """The joint genotype counts of every genome pair a <= b over the listed rows (kgx_pair_counts; rows None = the first
+        n_rows rows, every row by default): uint32 [G (G + 1) / 2][9] at pair_index(a, b, G), word 3 p + q = rows where a has
+        kind p and b kind q, kinds H, M, O."""
+        idx = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32)
+        if n_rows is None:
+            n_rows = self.n_variants if idx is None else len(idx)
+        out = np.zeros((self.n_genomes * (self.n_genomes + 1) // 2, 9), dtype=np.uint32)
+        check(lib().kgx_pair_counts(self._h, None if idx is None else ptr(idx), n_rows, ptr(out)))
+        return out
+
     def load_phase_plane(self, both_phases: np.ndarray, v0: int = 0) -> None:
         """both_phases: [rows][n_genomes] booleans -- the genome's copies of the row's variant sit on both phases."""
         bits = np.packbits(np.ascontiguousarray(both_phases, dtype=np.uint8), axis=1, bitorder="little")
@@ -526,6 +541,34 @@ class Population:
         out = np.zeros(4, dtype=np.uint64)
         check(lib().kgx_population_summary(self._h, ptr(out)))
         return out
+
+
+def pair_index(a: int, b: int, G: int) -> int:
+    """Where the pair a <= b of G genomes sits in the tables of pair_counts / pair_distances."""
+    return a * G - a * (a - 1) // 2 + (b - a)
+
+
+def pair_counts_last() -> tuple[float, int, int]:
+    """(product kernel ms, row batches, row slices of the grid) of the last pair_counts call (kgx_pair_counts_last)."""
+    ms, batches, splits = C.c_double(0.0), C.c_uint64(0), C.c_uint64(0)
+    check(lib().kgx_pair_counts_last(C.byref(ms), C.byref(batches), C.byref(splits)))
+    return float(ms.value), int(batches.value), int(splits.value)
+
+
+def pair_counts_last_panel_ms() -> float:
+    """Device time of the panel kernels of the last pair_counts call on the first slot's stream."""
+    return float(lib().kgx_pair_counts_last_panel_ms())
+
+
+def pair_distances(counts, n_genomes: int, n_rows: int, kind: int) -> np.ndarray:
+    """kgx_pair_distances: float64 [G (G + 1) / 2] from the pair_counts table -- kind 0 the IBS distance, kind 1 the
+    within-sample-frequency distance, over the jointly called rows (NaN where there is none).  Host only."""
+    c = np.ascontiguousarray(counts, dtype=np.uint32)
+    if c.shape != (n_genomes * (n_genomes + 1) // 2, 9):
+        raise ValueError("counts must be [G (G + 1) / 2][9]")
+    out = np.zeros(len(c), dtype=np.float64)
+    check(lib().kgx_pair_distances(ptr(c), int(n_genomes), int(n_rows), int(kind), ptr(out)))
+    return out
 
 
 def gene_genotypes_last_ms() -> float:
