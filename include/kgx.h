@@ -347,6 +347,42 @@ double kgx_pair_counts_last_panel_ms(void);
 int kgx_pair_distances(const uint32_t* counts /* [G(G+1)/2][9] */, uint64_t n_genomes, uint64_t n_rows,
                        int kind, double* out /* [G(G+1)/2] */);   /* host only */
 
+/* ---- Windowed joint genotype counts between variant ROWS: what linkage disequilibrium between loci is computed from.  The mirror
+ *      of kgx_pair_counts: two rows compared over the genomes, each list position against the next `window` positions.
+ * Kinds as above: H = code 1, M = code 2, O = code 3.  The listed rows are taken in the caller's order (normally position order;
+ * the call does not care).  For list position i and distance d in 0 .. window nine words at out[i][d]: word 3*p + q = the genomes
+ * in which row rows[i] has kind p and row rows[i + d] has kind q.  d = 0 holds the row's own H / M / O counts in words 0, 4 and 8
+ * and zero elsewhere; entries with i + d >= n_rows are zero; the counts involving code 0 are not stored -- they follow from the
+ * d = 0 entries and the genome count.  A row may be listed more than once: each position is its own.
+ * rows: host [n_rows]; NULL = rows 0 .. n_rows-1.  A row >= n_variants, or NULL rows with n_rows > n_variants: KGX_EINVAL.
+ * n_rows == 0 writes nothing.  window may exceed n_rows - 1 (the band is then the whole upper triangle, the rest zero).  A table
+ * whose byte size overflows 64 bits: KGX_EINVAL.  Counts are exact (int8 -> int32 products on the matrix cores).
+ * Honours the genome mask: a genome left out reads as code 0 in every row and adds to no stored word.
+ * Works over any binding: every shard counts over its own genomes straight from its rows (no panel, no transposition); shards on
+ * the first slot's device add into the one table there, a shard on another device fills a table there that is copied over and
+ * added.  The result does not depend on the binding.
+ * The table comes from the grow-only arena (kgx_release_scratch): list positions are processed in batches of whole 64-row blocks
+ * when a batch's part of the table (64 * blocks * (window + 1) * 36 bytes) would exceed a quarter of (free + arena).
+ * KGX_LD_ROWS=n caps the rows per batch (rounded up to a block) and KGX_LD_SPLITS=n the genome split below (both read at kgx_init /
+ * kgx_reload_options; unset or <= 0: no effect; each only ever lowers a number).  Neither batching nor splitting changes a result. */
+int kgx_ld_counts(kgx_pop* pop, const uint32_t* rows /* host [n_rows], or NULL = rows 0..n_rows-1 */, uint64_t n_rows,
+                  uint32_t window, uint32_t* out /* host [n_rows][window + 1][9] */);
+/* Of the last call: device time (HIP events, summed over the batches and the shards of the first slot's device) of the product
+ * kernel, the number of batches, and into how many slices the genomes' 512-genome segments were split over the grid (1 = not
+ * split; more where a batch has fewer pairs of 64-row blocks than two workgroups per compute unit -- the slices then add into a
+ * zeroed table).  Multiply-accumulates that the table stands for: 9 * n_rows * (window + 1) * G. */
+int kgx_ld_counts_last(double* kernel_ms, uint64_t* row_batches, uint64_t* genome_splits);
+/* The genotype (dosage) correlation r of every stored row pair.  Host only, no device.  This is THE LIBRARY'S definition -- the
+ * Pearson correlation of the two rows' dosages 0 / 1 / 2 over the jointly called genomes -- NOT a haplotype-phase r^2; r^2 is the
+ * caller's square.  n_genomes: the genomes taking part (those the mask keeps).  With H_i, M_i, O_i the d = 0 words of position i,
+ * j = i + d and n[p][q] the pair's words:  N = n_genomes - O_i - O_j + n[O][O];
+ *   Sx = (H_i - n[H][O]) + 2*(M_i - n[M][O]),  Sxx = (H_i - n[H][O]) + 4*(M_i - n[M][O]);  Sy, Syy likewise from j with n[O][H], n[O][M];
+ *   Sxy = n[H][H] + 2*n[H][M] + 2*n[M][H] + 4*n[M][M];  cov = N*Sxy - Sx*Sy,  vx = N*Sxx - Sx^2,  vy = N*Syy - Sy^2  (exact, 128-bit);
+ *   r = (double)cov / sqrt((double)vx * (double)vy).
+ * NaN where N == 0, vx == 0 or vy == 0, and for entries past the list's end. */
+int kgx_ld_statistics(const uint32_t* counts /* [n_rows][window + 1][9] */, uint64_t n_rows, uint32_t window,
+                      uint64_t n_genomes, double* r /* [n_rows][window + 1] */);   /* host only */
+
 /* ---- K4: VariantDBVariant::populationSummary (kgl_variant_db_variant.cpp:234-279). */
 int kgx_population_summary(kgx_pop* pop, uint64_t out[4]);
 

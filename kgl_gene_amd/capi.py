@@ -122,6 +122,9 @@ _SIGNATURES = {
     "kgx_pair_counts_last": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "kgx_pair_counts_last_panel_ms": (C.c_double, []),
     "kgx_pair_distances": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]),
+    "kgx_ld_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "kgx_ld_counts_last": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kgx_ld_statistics": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p]),
 }
 
 # kgx_gene_census (include/kgx.h), field for field
@@ -525,6 +528,17 @@ class Population:
         check(lib().kgx_pair_counts(self._h, None if idx is None else ptr(idx), n_rows, ptr(out)))
         return out
 
+    def ld_counts(self, rows=None, n_rows: int | None = None, window: int = 0) -> np.ndarray:
+        """The joint genotype counts of every list position with the next `window` positions over the genomes (kgx_ld_counts;
+        rows None = the first n_rows rows, every row by default): uint32 [n_rows][window + 1][9], word 3 p + q of [i][d] = genomes
+        where row rows[i] has kind p and row rows[i + d] kind q, kinds H, M, O; zero past the list's end."""
+        idx = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32)
+        if n_rows is None:
+            n_rows = self.n_variants if idx is None else len(idx)
+        out = np.zeros((n_rows, window + 1, 9), dtype=np.uint32)
+        check(lib().kgx_ld_counts(self._h, None if idx is None else ptr(idx), n_rows, window, ptr(out)))
+        return out
+
     def load_phase_plane(self, both_phases: np.ndarray, v0: int = 0) -> None:
         """both_phases: [rows][n_genomes] booleans -- the genome's copies of the row's variant sit on both phases."""
         bits = np.packbits(np.ascontiguousarray(both_phases, dtype=np.uint8), axis=1, bitorder="little")
@@ -568,6 +582,24 @@ def pair_distances(counts, n_genomes: int, n_rows: int, kind: int) -> np.ndarray
         raise ValueError("counts must be [G (G + 1) / 2][9]")
     out = np.zeros(len(c), dtype=np.float64)
     check(lib().kgx_pair_distances(ptr(c), int(n_genomes), int(n_rows), int(kind), ptr(out)))
+    return out
+
+
+def ld_counts_last() -> tuple[float, int, int]:
+    """(product kernel ms, batches of list positions, genome slices of the grid) of the last ld_counts call (kgx_ld_counts_last)."""
+    ms, batches, splits = C.c_double(0.0), C.c_uint64(0), C.c_uint64(0)
+    check(lib().kgx_ld_counts_last(C.byref(ms), C.byref(batches), C.byref(splits)))
+    return float(ms.value), int(batches.value), int(splits.value)
+
+
+def ld_statistics(counts, n_genomes: int) -> np.ndarray:
+    """kgx_ld_statistics: float64 [n_rows][window + 1] from the ld_counts table -- the genotype (dosage) correlation r of each
+    stored row pair over the jointly called genomes (NaN where undefined and past the list's end).  Host only."""
+    c = np.ascontiguousarray(counts, dtype=np.uint32)
+    if c.ndim != 3 or c.shape[1] < 1 or c.shape[2] != 9:
+        raise ValueError("counts must be [n_rows][window + 1][9]")
+    out = np.zeros(c.shape[:2], dtype=np.float64)
+    check(lib().kgx_ld_statistics(ptr(c), c.shape[0], c.shape[1] - 1, int(n_genomes), ptr(out)))
     return out
 
 
