@@ -383,6 +383,45 @@ int kgx_ld_counts_last(double* kernel_ms, uint64_t* row_batches, uint64_t* genom
 int kgx_ld_statistics(const uint32_t* counts /* [n_rows][window + 1][9] */, uint64_t n_rows, uint32_t window,
                       uint64_t n_genomes, double* r /* [n_rows][window + 1] */);   /* host only */
 
+/* ---- Runs of homozygosity per genome, and F_ROH: the share of a genome that lies in long unbroken stretches of homozygous calls --
+ *      the inbreeding estimator that needs no allele frequencies.  The reference's INBREED package stops at its four estimators;
+ *      these are THE LIBRARY'S definitions.  The one sweep that walks a genome along the rows IN ORDER, carrying state.
+ * Input: rows[n_rows], the listed rows in the caller's order (NULL = rows 0 .. n_rows-1, as in kgx_ld_counts; a row may be listed more
+ * than once: each position is its own); position[n_rows], the base positions of the list positions; contig_start[n_rows] or NULL
+ * (one contig): non-zero = this list position begins a new contig; position 0 always does.
+ * Cells, for one genome and one list position: code 1 is a HET; codes 0 and 2 are CALLED HOMOZYGOUS SITES; code 3 is a NO-CALL,
+ * which neither breaks a run nor counts as a site.
+ * There is a BREAK BEFORE list position i > 0 when contig_start[i] != 0, or when max_gap != 0 and position[i] - position[i-1] > max_gap.
+ * Runs: walk the list in order with an open run {first, last, sites}.  A break before i closes the open run, before i's own cell
+ * is looked at; a het closes it; a called site extends it (last = i, ++sites) or opens one (first = last = i, sites = 1); a no-call
+ * does nothing; the list's end closes it.  So a run begins and ends on called sites (no-calls at its ends are trimmed off), and its
+ * length = position[last] - position[first] + 1.  A closed run is REPORTED when sites >= min_sites and length >= min_length
+ * (min_sites == 0 behaves as 1, min_length == 0 as 1; params == NULL: 1, 1 and no gap rule).
+ * A genome the mask leaves out has no runs and its summary reads zero (as K3 / K8 report masked genomes).
+ * Output: per genome the summary over its reported runs; optionally the runs themselves under the sizing convention of
+ * kgx_genome_row_lists: begin[n_genomes + 1], segments[capacity][3] = {first, last, sites} in list positions, ascending per genome;
+ * segments == NULL sizes the call (begin[n_genomes] = entries needed); a capacity below that: KGX_EINVAL; begin == NULL and
+ * segments == NULL: summaries only, the fill pass is not run.
+ * KGX_EINVAL (the message names the index): a row >= n_variants; NULL rows with n_rows > n_variants; n_rows >= 2^32; position[i] <
+ * position[i-1] without a contig start at i; null pop, or null position or summary with n_rows > 0.  n_rows == 0 writes zero
+ * summaries and an all-zero begin.
+ * Everything is integers: the result does not depend on the binding, on how the rows are sliced, or on the run of the day.  Every
+ * shard walks its own genomes on its own device at the same time; nothing is exchanged.  Device buffers come from the grow-only arena
+ * (kgx_release_scratch): 76 bytes per (row slice, genome), the list's tables and the runs.  The list is cut into slices of whole
+ * 64-position tiles, enough for two waves on every SIMD, with the records within a quarter of (free + arena); KGX_ROH_SLICES=n caps
+ * the count (read at kgx_init / kgx_reload_options; unset or <= 0: no effect; it only ever lowers the count). */
+typedef struct kgx_roh_params { uint32_t min_sites; uint32_t min_length; uint32_t max_gap; } kgx_roh_params;
+typedef struct kgx_roh_summary { uint64_t runs, total_length, longest_length, sites_in_runs; } kgx_roh_summary;
+int kgx_roh(kgx_pop* pop, const uint32_t* rows /* host [n_rows], or NULL */, uint64_t n_rows, const uint32_t* position /* host [n_rows] */,
+            const uint8_t* contig_start /* host [n_rows], or NULL */, const kgx_roh_params* params, kgx_roh_summary* summary /* host [n_genomes] */,
+            uint64_t* begin /* host [n_genomes + 1] or NULL */, uint32_t* segments /* host [capacity][3] or NULL */, uint64_t capacity);
+/* Of the last call: device time (HIP events) of the count pass's walk, the slowest device's, and the row slices of the first shard.
+ * Algorithmic bytes: n_rows x ceil(G/4). */
+int kgx_roh_last(double* kernel_ms, uint64_t* row_slices);
+/* F_ROH.  Host only, no device: out[g] = (double)summary[g].total_length / (double)denominator -- ONE IEEE division; denominator 0:
+ * NaN.  The denominator (the callable genome length) is the caller's. */
+int kgx_roh_coefficients(const kgx_roh_summary* summary, uint64_t n_genomes, uint64_t denominator, double* out);
+
 /* ---- K4: VariantDBVariant::populationSummary (kgl_variant_db_variant.cpp:234-279). */
 int kgx_population_summary(kgx_pop* pop, uint64_t out[4]);
 

@@ -32,6 +32,10 @@ HIP_FLAGS = [
     # every one through a[0:3] around its MFMA (213 instead of 121 instructions per block, 156 instead of 118 registers).
     "-mllvm", "-amdgpu-mfma-vgpr-form",
 ]
+# Per translation unit, on top of HIP_FLAGS.  New units are compiled without gfx950's packed fp32 arithmetic (v_pk_add_f32,
+# v_pk_mul_f32, v_pk_fma_f32): kgx_roh.hip, whose device code is integers only.  hipcc hands the feature to its host pass as well,
+# which does not know it and says that it ignores it.
+UNIT_FLAGS = {"kgx_roh.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 OBJDIR = LIBDIR / "obj"
 
 
@@ -78,7 +82,7 @@ def build_kgx(force: bool = False, verbose: bool = False) -> Path:
         obj = OBJDIR / (src.stem + ".o")
         objects.append(obj)
         if force or extra or _stale(obj, [src] + _includes(src)):
-            cmd = [HIPCC, *HIP_FLAGS, *extra, "-I", str(ROOT / "include"), "-c", "-o", str(obj), str(src)]
+            cmd = [HIPCC, *HIP_FLAGS, *UNIT_FLAGS.get(src.name, []), *extra, "-I", str(ROOT / "include"), "-c", "-o", str(obj), str(src)]
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             jobs.append((cmd, subprocess.Popen(cmd, cwd=str(ROOT))))

@@ -125,12 +125,18 @@ _SIGNATURES = {
     "kgx_ld_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
     "kgx_ld_counts_last": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "kgx_ld_statistics": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p]),
+    "kgx_roh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "kgx_roh_last": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kgx_roh_coefficients": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
 }
 
 # kgx_gene_census (include/kgx.h), field for field
 GENE_CENSUS = np.dtype([("genomes", "<u8"), ("zero_variant_genomes", "<u8"), ("genotypes", "<u8"), ("variant_objects", "<u8"),
                         ("non_diploid_cells", "<u8"), ("unique_variants", "<u8"), ("singleton_variants", "<u8"), ("singleton_genomes", "<u8"),
                         ("top", "<u8", (5,))])
+
+# kgx_roh_summary (include/kgx.h), field for field
+ROH_SUMMARY = np.dtype([("runs", "<u8"), ("total_length", "<u8"), ("longest_length", "<u8"), ("sites_in_runs", "<u8")])
 
 
 def declared_symbols() -> list[str]:
@@ -539,6 +545,29 @@ class Population:
         check(lib().kgx_ld_counts(self._h, None if idx is None else ptr(idx), n_rows, window, ptr(out)))
         return out
 
+    def roh(self, position, rows=None, n_rows: int | None = None, contig_start=None, min_sites: int = 1, min_length: int = 1, max_gap: int = 0,
+            runs: bool = True):
+        """The runs of homozygosity of every genome along the listed rows (kgx_roh; all rows in order when `rows` is None):
+        (summary ROH_SUMMARY [n_genomes], begin uint64 [n_genomes + 1], segments uint32 [begin[-1]][3] = {first, last, sites} in
+        list positions), sized and then filled; runs=False: the summaries alone, (summary, None, None)."""
+        pos = np.ascontiguousarray(position, dtype=np.uint32)
+        idx = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32)
+        n_rows = int(n_rows if n_rows is not None else (len(pos) if idx is None else len(idx)))
+        starts = None if contig_start is None else np.ascontiguousarray(contig_start, dtype=np.uint8)
+        if len(pos) < n_rows or (idx is not None and len(idx) < n_rows) or (starts is not None and len(starts) < n_rows):
+            raise ValueError("position, rows and contig_start need n_rows entries each")
+        params = np.array([min_sites, min_length, max_gap], dtype=np.uint32)
+        summary = np.zeros(self.n_genomes, dtype=ROH_SUMMARY)
+        args = (self._h, None if idx is None else ptr(idx), n_rows, ptr(pos), None if starts is None else ptr(starts), ptr(params), ptr(summary))
+        if not runs:
+            check(lib().kgx_roh(*args, None, None, 0))
+            return summary, None, None
+        begin = np.zeros(self.n_genomes + 1, dtype=np.uint64)
+        check(lib().kgx_roh(*args, ptr(begin), None, 0))
+        segments = np.zeros((int(begin[-1]), 3), dtype=np.uint32)
+        check(lib().kgx_roh(*args, ptr(begin), ptr(segments), len(segments)))
+        return summary, begin, segments
+
     def load_phase_plane(self, both_phases: np.ndarray, v0: int = 0) -> None:
         """both_phases: [rows][n_genomes] booleans -- the genome's copies of the row's variant sit on both phases."""
         bits = np.packbits(np.ascontiguousarray(both_phases, dtype=np.uint8), axis=1, bitorder="little")
@@ -600,6 +629,21 @@ def ld_statistics(counts, n_genomes: int) -> np.ndarray:
         raise ValueError("counts must be [n_rows][window + 1][9]")
     out = np.zeros(c.shape[:2], dtype=np.float64)
     check(lib().kgx_ld_statistics(ptr(c), c.shape[0], c.shape[1] - 1, int(n_genomes), ptr(out)))
+    return out
+
+
+def roh_last() -> tuple[float, int]:
+    """(ms of the count pass's walk on the slowest device, row slices of the first shard) of the last roh call (kgx_roh_last)."""
+    ms, slices = C.c_double(0.0), C.c_uint64(0)
+    check(lib().kgx_roh_last(C.byref(ms), C.byref(slices)))
+    return ms.value, slices.value
+
+
+def roh_coefficients(summary, denominator: int) -> np.ndarray:
+    """kgx_roh_coefficients: F_ROH float64 [n_genomes] = total_length / denominator (NaN for denominator 0).  Host only."""
+    s = np.ascontiguousarray(summary, dtype=ROH_SUMMARY)
+    out = np.zeros(len(s), dtype=np.float64)
+    check(lib().kgx_roh_coefficients(ptr(s), len(s), int(denominator), ptr(out)))
     return out
 
 
