@@ -422,6 +422,48 @@ int kgx_roh_last(double* kernel_ms, uint64_t* row_slices);
  * NaN.  The denominator (the callable genome length) is the caller's. */
 int kgx_roh_coefficients(const kgx_roh_summary* summary, uint64_t n_genomes, uint64_t denominator, double* out);
 
+/* ---- Shared runs between genome pairs (identity-by-state segments, summarised): how much of the listed rows two genomes share in
+ *      long unbroken stretches -- the screen for identity by descent and clonality that kgx_pair_counts' order-free totals cannot
+ *      give and kgx_roh, which sees one genome at a time, does not.  The reference has no counterpart; these are THE LIBRARY'S
+ *      definitions.
+ * Pairs: the unordered pairs a <= b of the WHOLE population at kgx_pair_counts' pair index a*G - a*(a-1)/2 + (b - a).
+ * rows, position, contig_start and the BREAK rule are exactly kgx_roh's: a break before list position i > 0 when contig_start[i] != 0,
+ * or when max_gap != 0 and position[i] - position[i-1] > max_gap; rows in the caller's order, a row may be listed twice, NULL = rows
+ * 0 .. n_rows-1; positions non-decreasing within a contig.
+ * Cells, for one pair and one list position, ca and cb the two codes: a NO-CALL if either is 3 -- it neither breaks a run nor counts
+ * as a site; otherwise a MISMATCH under the mode -- KGX_SHARE_IBS0: {ca, cb} == {0, 2} (opposite homozygotes; a het on either side
+ * never mismatches), KGX_SHARE_IDENTICAL: ca != cb; otherwise a SHARED SITE.
+ * The walk is kgx_roh's with "het" replaced by "mismatch": a break closes the open run before the cell is looked at; a mismatch
+ * closes it; a shared site extends or opens it; a no-call does nothing; the list's end closes it.  length = position[last] -
+ * position[first] + 1; a closed run is REPORTED when sites >= max(min_sites, 1) and length >= max(min_length, 1).  params == NULL:
+ * 1, 1, no gap rule, KGX_SHARE_IBS0.  out[pair] = {runs, total_length, longest_length, sites_in_runs} over the reported runs; the
+ * runs themselves do not leave the device.
+ * The diagonal pair (a, a) follows the same rule: it never mismatches, so its runs are the genome's called stretches between breaks.
+ * Every pair that involves a genome the mask leaves out reads all zero.
+ * KGX_EINVAL (the message names the index) as in kgx_roh: a row >= n_variants; NULL rows with n_rows > n_variants; n_rows >= 2^32;
+ * position[i] < position[i-1] without a contig start at i; null pop, or null position or out with n_rows > 0; and a mode other than
+ * the two.  n_rows == 0 writes zero summaries.
+ * Everything is integers: the result depends neither on the binding nor on the batching.  Every shard turns the listed rows of its
+ * genomes into kgx_pair_counts' genome-major panel on its device, the panels are copied behind one another on the FIRST slot's
+ * device and the walk runs there, one workgroup per pair of 32-genome tiles for the whole list.  The table (48 bytes a pair: the
+ * summary and the run open between two batches), the list's tables and one panel batch come from the grow-only arena
+ * (kgx_release_scratch): rows are processed in batches of whole 64-row tiles when the panel would exceed a quarter of (free + arena)
+ * on a device; a table that does not fit beside one 64-row panel: KGX_ENOMEM.  KGX_PAIR_RUNS_ROWS=n (read at kgx_init /
+ * kgx_reload_options; unset or <= 0: no effect; it only ever lowers the number) caps the rows per batch, rounded up to 64. */
+#define KGX_SHARE_IBS0       0   /* a mismatch = opposite homozygotes: codes {0,2} or {2,0} */
+#define KGX_SHARE_IDENTICAL  1   /* a mismatch = the two codes differ                         */
+typedef struct kgx_pair_runs_params { uint32_t min_sites, min_length, max_gap, mode; } kgx_pair_runs_params;
+int kgx_pair_runs(kgx_pop* pop, const uint32_t* rows /* host [n_rows] or NULL */, uint64_t n_rows,
+                  const uint32_t* position /* host [n_rows] */, const uint8_t* contig_start /* host [n_rows] or NULL */,
+                  const kgx_pair_runs_params* params, kgx_roh_summary* out /* host [G(G+1)/2] */);
+/* Of the last call: device time (HIP events, summed over the row batches) of the walk kernel, and the number of row batches.
+ * Pair-tiles walked: G(G+1)/2 * ceil(n_rows / 64). */
+int kgx_pair_runs_last(double* kernel_ms, uint64_t* row_batches);
+/* The share of the genome two samples have in shared runs.  Host only, no device: out[p] = (double)summary[p].total_length /
+ * (double)denominator -- ONE IEEE division; denominator 0: NaN.  The denominator (the callable genome length) is the caller's. */
+int kgx_pair_run_fractions(const kgx_roh_summary* summary /* [G(G+1)/2] */, uint64_t n_genomes, uint64_t denominator,
+                           double* out /* [G(G+1)/2] */);   /* host only */
+
 /* ---- K4: VariantDBVariant::populationSummary (kgl_variant_db_variant.cpp:234-279). */
 int kgx_population_summary(kgx_pop* pop, uint64_t out[4]);
 

@@ -128,7 +128,13 @@ _SIGNATURES = {
     "kgx_roh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "kgx_roh_last": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kgx_roh_coefficients": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "kgx_pair_runs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kgx_pair_runs_last": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kgx_pair_run_fractions": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
 }
+
+# the modes of kgx_pair_runs (include/kgx.h)
+KGX_SHARE_IBS0, KGX_SHARE_IDENTICAL = 0, 1
 
 # kgx_gene_census (include/kgx.h), field for field
 GENE_CENSUS = np.dtype([("genomes", "<u8"), ("zero_variant_genomes", "<u8"), ("genotypes", "<u8"), ("variant_objects", "<u8"),
@@ -568,6 +574,23 @@ class Population:
         check(lib().kgx_roh(*args, ptr(begin), ptr(segments), len(segments)))
         return summary, begin, segments
 
+    def pair_runs(self, position, rows=None, n_rows: int | None = None, contig_start=None, min_sites: int = 1, min_length: int = 1,
+                  max_gap: int = 0, mode: int = KGX_SHARE_IBS0) -> np.ndarray:
+        """The shared runs of every genome pair a <= b along the listed rows (kgx_pair_runs; all rows in order when `rows` is None):
+        uint64 [G (G + 1) / 2][4] = {runs, total_length, longest_length, sites_in_runs} at pair_index(a, b, G).  mode: KGX_SHARE_IBS0
+        (opposite homozygotes mismatch) or KGX_SHARE_IDENTICAL (any two different codes do)."""
+        pos = np.ascontiguousarray(position, dtype=np.uint32)
+        idx = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32)
+        n_rows = int(n_rows if n_rows is not None else (len(pos) if idx is None else len(idx)))
+        starts = None if contig_start is None else np.ascontiguousarray(contig_start, dtype=np.uint8)
+        if len(pos) < n_rows or (idx is not None and len(idx) < n_rows) or (starts is not None and len(starts) < n_rows):
+            raise ValueError("position, rows and contig_start need n_rows entries each")
+        params = np.array([min_sites, min_length, max_gap, mode], dtype=np.uint32)
+        out = np.zeros((self.n_genomes * (self.n_genomes + 1) // 2, 4), dtype=np.uint64)
+        check(lib().kgx_pair_runs(self._h, None if idx is None else ptr(idx), n_rows, ptr(pos), None if starts is None else ptr(starts), ptr(params),
+                                  ptr(out)))
+        return out
+
     def load_phase_plane(self, both_phases: np.ndarray, v0: int = 0) -> None:
         """both_phases: [rows][n_genomes] booleans -- the genome's copies of the row's variant sit on both phases."""
         bits = np.packbits(np.ascontiguousarray(both_phases, dtype=np.uint8), axis=1, bitorder="little")
@@ -644,6 +667,24 @@ def roh_coefficients(summary, denominator: int) -> np.ndarray:
     s = np.ascontiguousarray(summary, dtype=ROH_SUMMARY)
     out = np.zeros(len(s), dtype=np.float64)
     check(lib().kgx_roh_coefficients(ptr(s), len(s), int(denominator), ptr(out)))
+    return out
+
+
+def pair_runs_last() -> tuple[float, int]:
+    """(walk kernel ms summed over the row batches, row batches) of the last pair_runs call (kgx_pair_runs_last)."""
+    ms, batches = C.c_double(0.0), C.c_uint64(0)
+    check(lib().kgx_pair_runs_last(C.byref(ms), C.byref(batches)))
+    return ms.value, batches.value
+
+
+def pair_run_fractions(summary, n_genomes: int, denominator: int) -> np.ndarray:
+    """kgx_pair_run_fractions: float64 [G (G + 1) / 2] = total_length / denominator of the pair_runs table (NaN for denominator 0).
+    Host only."""
+    s = np.ascontiguousarray(summary, dtype=np.uint64)
+    if s.shape != (n_genomes * (n_genomes + 1) // 2, 4):
+        raise ValueError("summary must be [G (G + 1) / 2][4]")
+    out = np.zeros(len(s), dtype=np.float64)
+    check(lib().kgx_pair_run_fractions(ptr(s), int(n_genomes), int(denominator), ptr(out)))
     return out
 
 

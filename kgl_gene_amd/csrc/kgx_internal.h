@@ -209,6 +209,13 @@ struct kgx_gt8 {
   std::vector<uint32_t> wide_loci;   // the rows that have a wide row (kgx_gt8_set_wide_rows), ascending: what the allele census refuses
 };
 
+namespace kgx {
+// The row list of a walk along the rows (kgx_roh, kgx_pair_runs) checked, and its break words: bit i & 63 of breaks[i >> 6] = a
+// break before list position i (a contig start, or a position step above max_gap != 0).  KGX_EINVAL names the index, after `who`.
+int run_breaks(const char* who, const kgx_pop* pop, const uint32_t* rows, uint64_t n_rows, const uint32_t* position, const uint8_t* contig_start,
+               uint32_t max_gap, std::vector<unsigned long long>& breaks);
+}  // namespace kgx
+
 #define KGX_HIP(call)                                                                             \
   do {                                                                                            \
     hipError_t kgx_err_ = (call);                                                                 \

@@ -9,7 +9,7 @@
 #ifndef KGX_KERNELS_ROH_H
 #define KGX_KERNELS_ROH_H
 
-#include "kgx_kernels_common.h"
+#include "kgx_kernels_runs.h"
 
 namespace kgx {
 
@@ -22,8 +22,6 @@ constexpr int kRohPlanes = 4;              // 16-byte planes of a slice record, 
 //   3: the interior runs' sites (64 bits)
 // Interior: opened after the slice's first event and closed inside the slice.
 constexpr uint64_t kRohBytesPerCell = kRohPlanes * 16 + 4 + 8;   // ... plus the (slice, genome) count and cursor
-
-struct RohRun { uint32_t first, last, sites; };             // list positions of the first and last called site; sites == 0: no run
 
 // The chunk's 2-bit codes as two rows of 64 bits: w[0], w[1] = het (code 1), low and high dword; w[2], w[3] = no-call (code 3).
 // The shift / mask ladder of carried_bits, once per plane.
@@ -84,10 +82,6 @@ __device__ __forceinline__ void roh_transpose(uint32_t (&w)[4], uint32_t lane) {
   roh_stage<1, 0x55555555u>(w, lane);
 }
 
-__device__ __forceinline__ bool roh_reported(uint32_t sites, unsigned long long length, uint32_t min_sites, uint32_t min_length) {
-  return sites >= min_sites && length >= min_length;
-}
-
 // A lane's state for one chunk column: the open run, carried from tile to tile, and what the slice's record is made of.
 struct RohLane {
   RohRun open, head;                       // head: the run the slice's first event closed
@@ -136,11 +130,8 @@ __device__ __forceinline__ void roh_close(RohLane& st, const uint32_t* strip, ui
 // reported interior runs' {first, last, sites} from cursors[slice][genome] on (k_roh_stitch<true> put the cursor behind the one
 // stitched run that may close in the slice).
 // Events of a tile: events = het | brk (brk: the tile's break word, one uniform load).  A het is never a called site and a break
-// before position b leaves b's own cell to the piece that follows, so both are handled alike: the called bits below the first
-// event fold into the open run, which closes; the called bits from the last event up open the next run; a piece between two
-// events of the tile is a whole run of at most 63 sites (62 after a het, 63 from a break at bit 0 to an event at bit 63) -- skipped unseen where min_sites is above that (the usual ROH filter: the
-// tile then costs the same whatever its hets), else tested by its popcount before anything else is done with it.  Without an
-// event the whole word folds in one step.
+// before position b leaves b's own cell to the piece that follows, so both are handled alike, by roh_walk_word
+// (kgx_kernels_runs.h, shared with the walk over genome pairs).
 // The list's end closes the open run in the last slice, as one more event.
 // Positions: lane i parks position[r0 + i] in the wave's own 256-byte strip of LDS, because the lanes ask for positions by a
 // divergent bit number from a divergent loop.  One wave writes and reads its strip, LDS serves a wave's accesses in order, so a
@@ -209,31 +200,7 @@ k_roh(const kgx_v4u* __restrict__ rows, uint32_t chunks_per_row, uint64_t n_geno
         open.last = static_cast<uint32_t>(r0) + 63u - static_cast<uint32_t>(__builtin_clzll(piece));
         open.sites += static_cast<uint32_t>(__builtin_popcountll(piece));
       };
-      if (events == 0) {
-        fold(called);                                         // inside a long run: one merge, no loop
-      } else {
-        // the piece below the first event closes with the carried run; the piece from the last event up opens the next one
-        const uint32_t first_event = static_cast<uint32_t>(__builtin_ctzll(events)), last_event = 63u - static_cast<uint32_t>(__builtin_clzll(events));
-        fold(called & ((1ull << first_event) - 1ull));
-        roh_close<FILL>(st[k], strip, r0, position, min_sites, min_length, segments);
-        if (min_sites <= 63u) {
-          // a run between two events of one tile has at most 63 sites (a break's own cell belongs to the piece that follows it, so a
-          // break at bit 0 and an event at bit 63 leave 63): only up to that bound are they looked at, and only those
-          // with enough sites become runs at all
-          unsigned long long pending = events & (events - 1ull);
-          uint32_t from = first_event;
-          while (pending) {
-            const uint32_t to = static_cast<uint32_t>(__builtin_ctzll(pending));
-            pending &= pending - 1ull;
-            const unsigned long long piece = called & ((1ull << to) - 1ull) & ~((1ull << from) - 1ull);
-            from = to;
-            if (static_cast<uint32_t>(__builtin_popcountll(piece)) < min_sites) continue;
-            fold(piece);
-            roh_close<FILL>(st[k], strip, r0, position, min_sites, min_length, segments);
-          }
-        }
-        fold(called & ~((1ull << last_event) - 1ull));
-      }
+      roh_walk_word(events, called, min_sites, fold, [&]() { roh_close<FILL>(st[k], strip, r0, position, min_sites, min_length, segments); });
     }
   }
 

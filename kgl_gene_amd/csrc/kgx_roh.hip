@@ -269,6 +269,23 @@ int roh_impl(RohCall& call, kgx_roh_summary* summary, uint64_t* begin, uint32_t*
 }
 
 }  // namespace
+
+int run_breaks(const char* who, const kgx_pop* pop, const uint32_t* rows, uint64_t n_rows, const uint32_t* position, const uint8_t* contig_start,
+               uint32_t max_gap, std::vector<unsigned long long>& breaks) {
+  breaks.assign((n_rows + 63) / 64, 0ull);
+  for (uint64_t i = 0; i < n_rows; ++i) {
+    if (rows && rows[i] >= pop->n_variants)
+      return fail(KGX_EINVAL, "%s: rows[%llu] = %u is not a row of the population's %llu", who, (unsigned long long)i, rows[i], (unsigned long long)pop->n_variants);
+    if (i == 0) continue;                                     // position 0 begins the first contig: no break before it
+    const bool contig = contig_start && contig_start[i] != 0;
+    if (!contig && position[i] < position[i - 1])
+      return fail(KGX_EINVAL, "%s: position[%llu] = %u is below position[%llu] = %u without a contig start", who, (unsigned long long)i, position[i],
+                  (unsigned long long)(i - 1), position[i - 1]);
+    if (contig || (max_gap != 0 && position[i] - position[i - 1] > max_gap)) breaks[i >> 6] |= 1ull << (i & 63);
+  }
+  return KGX_OK;
+}
+
 }  // namespace kgx
 
 using namespace kgx;
@@ -285,18 +302,8 @@ int kgx_roh(kgx_pop* pop, const uint32_t* rows, uint64_t n_rows, const uint32_t*
     if (n_rows >= (1ull << 32)) return fail(KGX_EINVAL, "roh: n_rows %llu exceeds the 32-bit list positions of the runs", (unsigned long long)n_rows);
     if (!rows && n_rows > pop->n_variants)
       return fail(KGX_EINVAL, "roh: n_rows %llu exceeds the population's %llu rows", (unsigned long long)n_rows, (unsigned long long)pop->n_variants);
-    const uint32_t max_gap = params ? params->max_gap : 0;
-    std::vector<unsigned long long> breaks((n_rows + 63) / 64, 0ull);
-    for (uint64_t i = 0; i < n_rows; ++i) {
-      if (rows && rows[i] >= pop->n_variants)
-        return fail(KGX_EINVAL, "roh: rows[%llu] = %u is not a row of the population's %llu", (unsigned long long)i, rows[i], (unsigned long long)pop->n_variants);
-      if (i == 0) continue;                                   // position 0 begins the first contig: no break before it
-      const bool contig = contig_start && contig_start[i] != 0;
-      if (!contig && position[i] < position[i - 1])
-        return fail(KGX_EINVAL, "roh: position[%llu] = %u is below position[%llu] = %u without a contig start", (unsigned long long)i, position[i],
-                    (unsigned long long)(i - 1), position[i - 1]);
-      if (contig || (max_gap != 0 && position[i] - position[i - 1] > max_gap)) breaks[i >> 6] |= 1ull << (i & 63);
-    }
+    std::vector<unsigned long long> breaks;
+    if (int rc = run_breaks("roh", pop, rows, n_rows, position, contig_start, params ? params->max_gap : 0, breaks)) return rc;
     g_last_roh_ms = 0.0;
     g_last_roh_slices = 0;
     if (summary) std::memset(summary, 0, pop->n_genomes * sizeof(kgx_roh_summary));
