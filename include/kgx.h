@@ -464,6 +464,51 @@ int kgx_pair_runs_last(double* kernel_ms, uint64_t* row_batches);
 int kgx_pair_run_fractions(const kgx_roh_summary* summary /* [G(G+1)/2] */, uint64_t n_genomes, uint64_t denominator,
                            double* out /* [G(G+1)/2] */);   /* host only */
 
+/* ---- Per-row score tables between genome pairs, and the genomic relationship matrix (GRM) from them: the WEIGHTED product over
+ *      the listed rows that the nine unweighted counts of kgx_pair_counts cannot give -- every row carries its own four values.
+ *      The reference has no counterpart; these are THE LIBRARY'S definitions.
+ * tables[i][c] is the value of genotype code c (0 .. 3) in list position i.  For every unordered pair a <= b of the WHOLE population,
+ * at kgx_pair_counts' pair index a*G - a*(a-1)/2 + (b - a):
+ *     out[pair] = sum over i of  tables[i][code(a, rows[i])] * tables[i][code(b, rows[i])]          (an exact int64)
+ * rows as in kgx_pair_counts: host [n_rows], any order, a row listed twice counts twice (each position with its own table), NULL =
+ * rows 0 .. n_rows-1.  KGX_EINVAL: a row >= n_variants; NULL rows with n_rows > n_variants; |tables[i][c]| > KGX_SCORE_MAX (the
+ * message names i and c); n_rows >= 2^32 (below that |out| < 2^58); null pop or out, or null tables with n_rows > 0.  n_rows == 0
+ * writes zeros.
+ * Exact: each value is split into two signed base-128 digits, the digit products run int8 -> int32 on the matrix cores, at most
+ * KGX_SCORE_ACC_ROWS rows into one int32 accumulation, and are put together in int64; the result depends neither on the binding
+ * nor on the batching.  Honours the genome mask: a genome left out scores 0 with every genome, itself included (it does NOT read
+ * as code 0, whose value is generally not 0).
+ * Works over any binding like kgx_pair_counts: every shard builds its genomes' panel on its device, the product runs on the FIRST
+ * slot's.  The table (8*G*(G+1)/2 bytes), the batch's digit tables (8 bytes a row) and one panel batch come from the grow-only
+ * arena (kgx_release_scratch): rows are processed in batches of whole 64-row steps when the panel would exceed a quarter of
+ * (free + arena) on a device; a table that does not fit beside one 64-row panel: KGX_ENOMEM.  KGX_SCORES_ROWS=n caps the rows per
+ * batch (rounded up to 64) and KGX_SCORES_SPLITS=n the slices below (both read at kgx_init / kgx_reload_options; unset or <= 0: no
+ * effect; each only ever lowers a number). */
+#define KGX_SCORE_MAX 8128
+#define KGX_SCORE_ACC_ROWS 131072   /* rows one workgroup accumulates in int32 in one launch: 2048 64-row steps */
+int kgx_pair_scores(kgx_pop* pop, const uint32_t* rows /* host [n_rows] or NULL */, uint64_t n_rows,
+                    const int16_t* tables /* host [n_rows][4]: the value of codes 0, 1, 2, 3 in list position i */,
+                    int64_t* out /* host [G(G+1)/2] */);
+/* Of the last call: device time (HIP events, summed over the row batches) of the product kernel, the number of row batches, and
+ * into how many slices the steps of a batch were split over the grid (1 = not split).  Multiply-accumulates of the product as the
+ * digits run it: 4 * G(G+1)/2 * n_rows. */
+int kgx_pair_scores_last(double* kernel_ms, uint64_t* row_batches, uint64_t* row_splits);
+/* The GRM  G_ab = (1/m) sum_r z_ar z_br,  z_gr = (x_gr - 2 p_r) / sqrt(2 p_r (1 - p_r)),  as score tables.  Host only, no device.
+ * row_counts[i] = the counts of codes 0 .. 3 of LISTED row i (as kgx_allele_count_by_locus gives them).  Per row: called = c0 + c1 +
+ * c2, p = (c1 + 2 c2) / (2 called); the row is USED iff called > 0, min(p, 1-p) > 0 and min(p, 1-p) >= min_maf -- otherwise its
+ * table is all zero.  For a used row z(d) = (d - 2p) / sqrt(2p(1-p)) for d = 0, 1, 2 and z(code 3) = 0 (mean imputation);
+ * tables[i][c] = llrint(z(c) * 2^scale_bits).  *scale_bits in: 0 .. 12, or < 0 = choose the largest s <= 12 at which every entry is
+ * within KGX_SCORE_MAX; out: the one used.  A given s at which an entry does not fit (the message names the row), s > 12, or a null
+ * argument: KGX_EINVAL.  *rows_used = m.
+ * kgx_grm_finish: out[pair] = (double)scores[pair] / (double)(rows_used * 4^scale_bits) -- ONE conversion and ONE IEEE division;
+ * rows_used == 0 gives NaN.
+ * The result is EXACTLY the GRM of the quantised z (tables / 2^s): the product adds no error of its own.  kgx_grm_tables decides
+ * the quantisation and nothing else does. */
+int kgx_grm_tables(const uint32_t* row_counts /* [n_rows][4] */, uint64_t n_rows, double min_maf, int* scale_bits,
+                   int16_t* tables /* [n_rows][4] */, uint64_t* rows_used);   /* host only */
+int kgx_grm_finish(const int64_t* scores /* [G(G+1)/2] */, uint64_t n_genomes, int scale_bits, uint64_t rows_used,
+                   double* out /* [G(G+1)/2] */);   /* host only */
+
 /* ---- K4: VariantDBVariant::populationSummary (kgl_variant_db_variant.cpp:234-279). */
 int kgx_population_summary(kgx_pop* pop, uint64_t out[4]);
 

@@ -131,7 +131,14 @@ _SIGNATURES = {
     "kgx_pair_runs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kgx_pair_runs_last": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kgx_pair_run_fractions": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "kgx_pair_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "kgx_pair_scores_last": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kgx_grm_tables": (C.c_int, [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kgx_grm_finish": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_void_p]),
 }
+
+# kgx_pair_scores (include/kgx.h): the largest table entry, and the rows one workgroup accumulates in int32 in one launch
+SCORE_MAX, SCORE_ACC_ROWS = 8128, 131072
 
 # the modes of kgx_pair_runs (include/kgx.h)
 KGX_SHARE_IBS0, KGX_SHARE_IDENTICAL = 0, 1
@@ -591,6 +598,20 @@ class Population:
                                   ptr(out)))
         return out
 
+    def pair_scores(self, tables, rows=None, n_rows: int | None = None) -> np.ndarray:
+        """The score of every genome pair a <= b over the listed rows (kgx_pair_scores; rows None = the first n_rows rows): int64
+        [G (G + 1) / 2] at pair_index(a, b, G) = sum over list positions i of tables[i][code of a] * tables[i][code of b], exact.
+        tables: int16 [n_rows][4], |entry| <= SCORE_MAX."""
+        tab = np.ascontiguousarray(tables, dtype=np.int16)
+        idx = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32)
+        if n_rows is None:
+            n_rows = len(tab) if idx is None else len(idx)
+        if tab.shape != (n_rows, 4) or (idx is not None and len(idx) < n_rows):
+            raise ValueError("tables must be [n_rows][4] and rows needs n_rows entries")
+        out = np.zeros(self.n_genomes * (self.n_genomes + 1) // 2, dtype=np.int64)
+        check(lib().kgx_pair_scores(self._h, None if idx is None else ptr(idx), n_rows, ptr(tab), ptr(out)))
+        return out
+
     def load_phase_plane(self, both_phases: np.ndarray, v0: int = 0) -> None:
         """both_phases: [rows][n_genomes] booleans -- the genome's copies of the row's variant sit on both phases."""
         bits = np.packbits(np.ascontiguousarray(both_phases, dtype=np.uint8), axis=1, bitorder="little")
@@ -685,6 +706,35 @@ def pair_run_fractions(summary, n_genomes: int, denominator: int) -> np.ndarray:
         raise ValueError("summary must be [G (G + 1) / 2][4]")
     out = np.zeros(len(s), dtype=np.float64)
     check(lib().kgx_pair_run_fractions(ptr(s), int(n_genomes), int(denominator), ptr(out)))
+    return out
+
+
+def pair_scores_last() -> tuple[float, int, int]:
+    """(product kernel ms, row batches, row slices of the grid) of the last pair_scores call (kgx_pair_scores_last)."""
+    ms, batches, splits = C.c_double(0.0), C.c_uint64(0), C.c_uint64(0)
+    check(lib().kgx_pair_scores_last(C.byref(ms), C.byref(batches), C.byref(splits)))
+    return float(ms.value), int(batches.value), int(splits.value)
+
+
+def grm_tables(row_counts, min_maf: float = 0.0, scale_bits: int = -1) -> tuple[np.ndarray, int, int]:
+    """kgx_grm_tables: the score tables of the genomic relationship matrix from the listed rows' code counts [n_rows][4] ->
+    (tables int16 [n_rows][4], the scale_bits used, rows_used).  scale_bits < 0: the largest that fits.  Host only."""
+    counts = np.ascontiguousarray(row_counts, dtype=np.uint32)
+    if counts.ndim != 2 or counts.shape[1] != 4:
+        raise ValueError("row_counts must be [n_rows][4]")
+    tables = np.zeros((len(counts), 4), dtype=np.int16)
+    bits, used = C.c_int(scale_bits), C.c_uint64(0)
+    check(lib().kgx_grm_tables(ptr(counts), len(counts), float(min_maf), C.byref(bits), ptr(tables), C.byref(used)))
+    return tables, int(bits.value), int(used.value)
+
+
+def grm_finish(scores, n_genomes: int, scale_bits: int, rows_used: int) -> np.ndarray:
+    """kgx_grm_finish: float64 [G (G + 1) / 2] = scores / (rows_used * 4^scale_bits) (NaN for rows_used 0).  Host only."""
+    s = np.ascontiguousarray(scores, dtype=np.int64)
+    if s.shape != (n_genomes * (n_genomes + 1) // 2,):
+        raise ValueError("scores must be [G (G + 1) / 2]")
+    out = np.zeros(len(s), dtype=np.float64)
+    check(lib().kgx_grm_finish(ptr(s), int(n_genomes), int(scale_bits), int(rows_used), ptr(out)))
     return out
 
 

@@ -1,4 +1,5 @@
-// Internal declarations shared by the C-ABI translation units (kgx_runtime.hip, kgx_dosage.hip, kgx_inbreed.hip).
+// Internal declarations shared by the C-ABI translation units (kgx_runtime.hip, kgx_dosage.hip, kgx_inbreed.hip, ...), and at
+// the end the small helpers that more than one driver uses (EventPair, available_bytes, pair_index, PanelShards).
 //
 // A Runtime is one binding of the library to a list of devices (kgx_init).  Every handle keeps the Runtime it was
 // created under alive and owns one shard per device slot; nothing per-device lives in process globals -- the only
@@ -9,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <atomic>
 #include <memory>
 #include <mutex>
@@ -235,5 +237,99 @@ int run_breaks(const char* who, const kgx_pop* pop, const uint32_t* rows, uint64
                          __FILE__, __LINE__);                                                     \
     }                                                                                             \
   } while (0)
+
+namespace kgx {
+
+// HIP events of one call, destroyed with it.
+struct EventPair {
+  hipEvent_t begin = nullptr, end = nullptr;
+  double ms = 0.0;
+  ~EventPair() {
+    if (begin) (void)hipEventDestroy(begin);
+    if (end) (void)hipEventDestroy(end);
+  }
+  int create() {
+    KGX_HIP(hipEventCreate(&begin));
+    KGX_HIP(hipEventCreate(&end));
+    return KGX_OK;
+  }
+  void collect() {
+    float t = 0.f;
+    if (hipEventElapsedTime(&t, begin, end) == hipSuccess) ms += t;
+    else (void)hipGetLastError();
+  }
+};
+
+// What a call may plan with on the current device (= dev).
+inline uint64_t available_bytes(const Device& dev) {
+  size_t free_bytes = 0, total_bytes = 0;
+  if (hipMemGetInfo(&free_bytes, &total_bytes) != hipSuccess) { (void)hipGetLastError(); free_bytes = 0; }
+  return static_cast<uint64_t>(free_bytes) + dev.scratch_bytes;          // the arena counts as free: it is re-used
+}
+
+// Where the pair a <= b of G genomes sits in a table of genome pairs.
+inline uint64_t pair_index(uint64_t a, uint64_t b, uint64_t G) { return a * G - a * (a - 1) / 2 + (b - a); }
+
+// The products over the genome-major panel (kgx_pair_counts, kgx_pair_scores) run on the first shard's device; shards on the same
+// HIP device share its stream and arena and write straight into its panel, a shard elsewhere builds its part there (its own copy
+// of the row list, its own panel in that device's arena) and copies it over per batch.
+struct PanelShard { Device* dev = nullptr; bool foreign = false; const uint32_t* d_list = nullptr; uint8_t* d_panel = nullptr; };
+struct PanelShards {
+  std::vector<PanelShard> sb;                                 // one per shard of the population
+  std::vector<Device*> foreign;                               // the other devices that hold genomes
+  std::vector<std::unique_lock<std::mutex>> locks;            // the first device's mutex, then theirs
+
+  explicit PanelShards(const kgx_pop* pop) : sb(pop->shards.size()) {
+    Device& cdev = *pop->shards[0].dev;
+    for (size_t s = 0; s < pop->shards.size(); ++s) {
+      Device* d = pop->shards[s].dev;
+      sb[s].foreign = d->id != cdev.id;
+      sb[s].dev = sb[s].foreign ? d : &cdev;
+      bool known = false;
+      for (Device* f : foreign) known = known || f == d;
+      if (sb[s].foreign && pop->shards[s].n_genomes && !known) foreign.push_back(d);
+    }
+    locks.emplace_back(cdev.mutex);
+    for (Device* d : foreign) locks.emplace_back(d->mutex);
+  }
+
+  // The 64-row tiles of a batch that the other devices have room for: a panel of the shard's genomes (padded to `tile` of them)
+  // and the row list within a quarter of (free + arena) there.  Lowers batch_tiles only.
+  int fit_elsewhere(const kgx_pop* pop, uint64_t tile, uint64_t list_bytes, uint64_t& batch_tiles) const {
+    for (size_t s = 0; s < pop->shards.size(); ++s) {
+      if (!sb[s].foreign || pop->shards[s].n_genomes == 0) continue;
+      if (int rc = use_device(*sb[s].dev)) return rc;
+      const uint64_t shard_padded = (pop->shards[s].n_genomes + tile - 1) / tile * tile, there = available_bytes(*sb[s].dev);
+      batch_tiles = std::min(batch_tiles, (there / 4 > list_bytes ? there / 4 - list_bytes : 0) / (shard_padded * 16));
+    }
+    return KGX_OK;
+  }
+
+  // Every shard's list and panel pointers: d_list / d_panel are the first device's (rows null: no list); a shard elsewhere gets
+  // its own out of that device's arena, the list copied there.
+  int reserve(const kgx_pop* pop, uint64_t tile, const uint32_t* rows, uint64_t list_bytes, const uint32_t* d_list, uint8_t* d_panel, uint64_t panel_pitch) {
+    for (size_t s = 0; s < pop->shards.size(); ++s) {
+      const kgx_pop_shard& sh = pop->shards[s];
+      sb[s].d_list = d_list;
+      sb[s].d_panel = d_panel + sh.genome_base * panel_pitch;   // results go straight into the first device's panel
+      if (!sb[s].foreign || sh.n_genomes == 0) continue;
+      Device& dev = *sh.dev;
+      if (int rc = use_device(dev)) return rc;
+      ScratchPlan fplan;
+      const size_t f_list = fplan.add(list_bytes), f_panel = fplan.add((sh.n_genomes + tile - 1) / tile * tile * panel_pitch);
+      char* farena = nullptr;
+      if (int rc = scratch_reserve(dev, fplan.total, &farena)) return rc;
+      if (rows) {
+        KGX_HIP(hipMemcpyAsync(farena + f_list, rows, list_bytes, hipMemcpyHostToDevice, dev.stream));
+        KGX_HIP(hipStreamSynchronize(dev.stream));
+        sb[s].d_list = reinterpret_cast<const uint32_t*>(farena + f_list);
+      }
+      sb[s].d_panel = reinterpret_cast<uint8_t*>(farena + f_panel);
+    }
+    return KGX_OK;
+  }
+};
+
+}  // namespace kgx
 
 #endif  // KGX_INTERNAL_H

@@ -21,32 +21,6 @@ namespace {
 std::atomic<double> g_last_ld_ms{0.0};
 std::atomic<uint64_t> g_last_ld_batches{0}, g_last_ld_splits{0};
 
-// HIP events of one call, destroyed with it.
-struct EventPair {
-  hipEvent_t begin = nullptr, end = nullptr;
-  double ms = 0.0;
-  ~EventPair() {
-    if (begin) (void)hipEventDestroy(begin);
-    if (end) (void)hipEventDestroy(end);
-  }
-  int create() {
-    KGX_HIP(hipEventCreate(&begin));
-    KGX_HIP(hipEventCreate(&end));
-    return KGX_OK;
-  }
-  void collect() {
-    float t = 0.f;
-    if (hipEventElapsedTime(&t, begin, end) == hipSuccess) ms += t;
-    else (void)hipGetLastError();
-  }
-};
-
-uint64_t available_bytes(const Device& dev) {
-  size_t free_bytes = 0, total_bytes = 0;
-  if (hipMemGetInfo(&free_bytes, &total_bytes) != hipSuccess) { (void)hipGetLastError(); free_bytes = 0; }
-  return static_cast<uint64_t>(free_bytes) + dev.scratch_bytes;          // the arena counts as free: it is re-used
-}
-
 uint32_t segments_of(uint64_t genomes) { return static_cast<uint32_t>((genomes + 64u * kLdSegment - 1) / (64u * kLdSegment)); }
 
 int ld_counts_impl(kgx_pop* pop, const uint32_t* rows, uint64_t n_rows, uint32_t window, uint32_t* out) {

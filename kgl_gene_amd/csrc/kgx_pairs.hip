@@ -20,34 +20,6 @@ namespace {
 std::atomic<double> g_last_pairs_ms{0.0}, g_last_panel_ms{0.0};
 std::atomic<uint64_t> g_last_pairs_batches{0}, g_last_pairs_splits{0};
 
-// HIP events of one call, destroyed with it.
-struct EventPair {
-  hipEvent_t begin = nullptr, end = nullptr;
-  double ms = 0.0;
-  ~EventPair() {
-    if (begin) (void)hipEventDestroy(begin);
-    if (end) (void)hipEventDestroy(end);
-  }
-  int create() {
-    KGX_HIP(hipEventCreate(&begin));
-    KGX_HIP(hipEventCreate(&end));
-    return KGX_OK;
-  }
-  void collect() {
-    float t = 0.f;
-    if (hipEventElapsedTime(&t, begin, end) == hipSuccess) ms += t;
-    else (void)hipGetLastError();
-  }
-};
-
-uint64_t pair_index(uint64_t a, uint64_t b, uint64_t G) { return a * G - a * (a - 1) / 2 + (b - a); }
-
-uint64_t available_bytes(const Device& dev) {
-  size_t free_bytes = 0, total_bytes = 0;
-  if (hipMemGetInfo(&free_bytes, &total_bytes) != hipSuccess) { (void)hipGetLastError(); free_bytes = 0; }
-  return static_cast<uint64_t>(free_bytes) + dev.scratch_bytes;          // the arena counts as free: it is re-used
-}
-
 int pair_counts_impl(kgx_pop* pop, const uint32_t* rows, uint64_t n_rows, uint32_t* out) {
   const uint64_t G = pop->n_genomes, T = (G + kPairTile - 1) / kPairTile, padded = T * kPairTile;
   const uint64_t words = G * (G + 1) / 2 * kPairWords, list_bytes = rows ? n_rows * sizeof(uint32_t) : 0;
@@ -56,18 +28,9 @@ int pair_counts_impl(kgx_pop* pop, const uint32_t* rows, uint64_t n_rows, uint32
 
   // ---- devices: the product runs on the first shard's; shards on the same HIP device share its stream and arena
   Device& cdev = *pop->shards[0].dev;
-  struct ShardBuffers { Device* dev = nullptr; bool foreign = false; const uint32_t* d_list = nullptr; uint8_t* d_panel = nullptr; };
-  std::vector<ShardBuffers> sb(pop->shards.size());
-  std::vector<Device*> foreign;
-  for (size_t s = 0; s < pop->shards.size(); ++s) {
-    Device* d = pop->shards[s].dev;
-    sb[s].foreign = d->id != cdev.id;
-    sb[s].dev = sb[s].foreign ? d : &cdev;
-    if (sb[s].foreign && pop->shards[s].n_genomes && std::find(foreign.begin(), foreign.end(), d) == foreign.end()) foreign.push_back(d);
-  }
-  std::vector<std::unique_lock<std::mutex>> locks;
-  locks.emplace_back(cdev.mutex);
-  for (Device* d : foreign) locks.emplace_back(d->mutex);
+  PanelShards shards(pop);
+  std::vector<PanelShard>& sb = shards.sb;
+  const std::vector<Device*>& foreign = shards.foreign;
 
   // ---- rows per batch: the panel within a quarter of (free + arena) on every device; the triangle beside it on the first
   if (int rc = use_device(cdev)) return rc;
@@ -76,12 +39,7 @@ int pair_counts_impl(kgx_pop* pop, const uint32_t* rows, uint64_t n_rows, uint32
     return fail(KGX_ENOMEM, "pair_counts: the %llu-byte table of %llu genomes' pairs does not fit beside one 64-row panel into the %llu bytes free on the first device",
                 (unsigned long long)(words * sizeof(uint32_t)), (unsigned long long)G, (unsigned long long)available);
   uint64_t batch_tiles = std::min(available / 4, available - fixed) / (padded * 16);
-  for (size_t s = 0; s < pop->shards.size(); ++s) {
-    if (!sb[s].foreign || pop->shards[s].n_genomes == 0) continue;
-    if (int rc = use_device(*sb[s].dev)) return rc;
-    const uint64_t shard_padded = (pop->shards[s].n_genomes + kPairTile - 1) / kPairTile * kPairTile, there = available_bytes(*sb[s].dev);
-    batch_tiles = std::min(batch_tiles, (there / 4 > list_bytes ? there / 4 - list_bytes : 0) / (shard_padded * 16));
-  }
+  if (int rc = shards.fit_elsewhere(pop, kPairTile, list_bytes, batch_tiles)) return rc;
   batch_tiles = std::max<uint64_t>(1, std::min(batch_tiles, (n_rows + kPairTile - 1) / kPairTile));
   uint64_t batch_rows = std::min(batch_tiles * kPairTile, n_rows);
   const int forced = env_int("KGX_PAIRS_ROWS", 0);
@@ -102,25 +60,7 @@ int pair_counts_impl(kgx_pop* pop, const uint32_t* rows, uint64_t n_rows, uint32
     KGX_HIP(hipMemcpyAsync(arena + o_list, rows, list_bytes, hipMemcpyHostToDevice, cdev.stream));
     KGX_HIP(hipStreamSynchronize(cdev.stream));               // the source is pageable host memory
   }
-  for (size_t s = 0; s < pop->shards.size(); ++s) {
-    const kgx_pop_shard& sh = pop->shards[s];
-    sb[s].d_list = d_list;
-    sb[s].d_panel = d_panel + sh.genome_base * panel_pitch;   // results go straight into the first device's panel
-    if (!sb[s].foreign || sh.n_genomes == 0) continue;
-    // a shard elsewhere: its own copy of the row list and its own panel in that device's arena, copied over per batch
-    Device& dev = *sh.dev;
-    if (int rc = use_device(dev)) return rc;
-    ScratchPlan fplan;
-    const size_t f_list = fplan.add(list_bytes), f_panel = fplan.add((sh.n_genomes + kPairTile - 1) / kPairTile * kPairTile * panel_pitch);
-    char* farena = nullptr;
-    if (int rc = scratch_reserve(dev, fplan.total, &farena)) return rc;
-    if (rows) {
-      KGX_HIP(hipMemcpyAsync(farena + f_list, rows, list_bytes, hipMemcpyHostToDevice, dev.stream));
-      KGX_HIP(hipStreamSynchronize(dev.stream));
-      sb[s].d_list = reinterpret_cast<const uint32_t*>(farena + f_list);
-    }
-    sb[s].d_panel = reinterpret_cast<uint8_t*>(farena + f_panel);
-  }
+  if (int rc = shards.reserve(pop, kPairTile, rows, list_bytes, d_list, d_panel, panel_pitch)) return rc;
 
   // ---- how the product is cut: tile pairs, and the batch's steps over gridDim.z where the pairs alone leave the device idle
   if (int rc = use_device(cdev)) return rc;
