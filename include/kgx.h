@@ -509,6 +509,58 @@ int kgx_grm_tables(const uint32_t* row_counts /* [n_rows][4] */, uint64_t n_rows
 int kgx_grm_finish(const int64_t* scores /* [G(G+1)/2] */, uint64_t n_genomes, int scale_bits, uint64_t rows_used,
                    double* out /* [G(G+1)/2] */);   /* host only */
 
+/* ---- Association scan: per-row class sums of per-genome columns -- the row x per-genome-value product that every single-variant
+ *      association test, weighted allele frequency and per-genotype trait mean is computed from.  The reference has no counterpart;
+ *      these are THE LIBRARY'S definitions.
+ * columns[j][g] is the caller's value of genome g of the WHOLE population in column j (a phenotype, a covariate, an ancestry
+ * weight), |value| <= KGX_COLUMN_MAX.  With code(g, r) the 2-bit code (1 = H, 2 = M, 3 = O / no-call, as in kgx_ld_counts):
+ *     out[i][j][k] = sum over the genomes g with code(g, rows[i]) == k + 1 of  columns[j][g]                  (an exact int64)
+ * The code-0 sum is not stored: it is the column's total over the kept genomes minus the three stored sums.
+ * rows as in kgx_ld_counts: host [n_rows], any order, a row listed twice is two positions, NULL = rows 0 .. n_rows-1.
+ * KGX_EINVAL: |columns[j][g]| > KGX_COLUMN_MAX (the message names j and g); a row >= n_variants; NULL rows with n_rows > n_variants;
+ * n_columns == 0 with n_rows > 0; null pop, or null out or columns with n_rows > 0; a table whose byte size overflows 64 bits; a
+ * shard of more than 2^25 genomes (the bound of the int32 accumulation: 64 * 2^25 = 2^31).  n_rows == 0 writes nothing.
+ * Exact: the columns are taken in groups of 16, each split into 1 .. 4 signed base-128 digits in [-64, 63] (as many as the group's
+ * values need: this affects speed only); the indicator x digit products run int8 -> int32 on the matrix cores and are put together
+ * in int64 in registers.  Honours the genome mask: a genome left out adds to no word.
+ * Works over any binding like kgx_ld_counts: every shard sums over its own genomes straight from its rows; shards on the first slot's
+ * device add into the one table there, a shard on another device fills a table there that is copied over and added.  The result
+ * depends neither on the binding nor on batching nor on splitting.
+ * The table, the columns (4 bytes a value) and their digit operands (up to 4 bytes a value) come from the grow-only arena
+ * (kgx_release_scratch): list positions are processed in batches of whole 64-row blocks when a batch's part of the table (64 * blocks
+ * * n_columns * 24 bytes) would exceed a quarter of (free + arena).  KGX_ASSOC_ROWS=n caps the rows per batch (rounded up to a block)
+ * and KGX_ASSOC_SPLITS=n the genome slices below (both read at kgx_init / kgx_reload_options; unset or <= 0: no effect; each only
+ * ever lowers a number). */
+#define KGX_COLUMN_MAX 67108864   /* 2^26: what four signed base-128 digits hold with room; >= 8128^2 */
+int kgx_column_sums(kgx_pop* pop, const uint32_t* rows /* host [n_rows] or NULL */, uint64_t n_rows,
+                    const int32_t* columns /* host [n_columns][G], G = the WHOLE population's genomes */, uint32_t n_columns,
+                    int64_t* out /* host [n_rows][n_columns][3] */);
+/* Of the last call: device time (HIP events, summed over the batches and the shards of the first slot's device) of the product
+ * kernel, the number of batches, and into how many slices the genomes' 256-genome segments were split over the grid (1 = not
+ * split; more where a batch has fewer (64-row block, tile pass) pairs than two workgroups per compute unit -- the slices then add
+ * into a zeroed table).  Multiply-accumulates that the table stands for: 3 * n_rows * n_columns * G. */
+int kgx_column_sums_last(double* kernel_ms, uint64_t* row_batches, uint64_t* genome_splits);
+/* Traits as columns.  Host only, no device.  y[t][g] is trait t of genome g; q = llrint(y * 2^s); columns[t] = q_t and
+ * columns[n_traits + t] = q_t^2.  *scale_bits in: 0 .. 12, or < 0 = choose the largest s <= 12 at which every |q| <= 8128 (then
+ * q^2 <= KGX_COLUMN_MAX); out: the s used.  A non-finite y, or a given s at which a value does not fit (the message names the trait
+ * and the genome), s > 12, or a null argument: KGX_EINVAL.  A MISSING phenotype has no encoding here: the caller removes such
+ * genomes with the genome mask (kgx_population_set_genome_mask) and passes any finite value for them. */
+int kgx_assoc_columns(const double* y /* [n_traits][G] */, uint64_t n_genomes, uint32_t n_traits, int* scale_bits,
+                      int32_t* columns /* [2 * n_traits][G] */);   /* host only */
+/* The scan itself.  Host only, no device: the least-squares regression of the QUANTISED trait q / 2^s on the dosage 0 / 1 / 2 over
+ * the called genomes of the row.  sums: kgx_column_sums of the columns of kgx_assoc_columns; row_counts: the listed rows' code
+ * counts as kgx_allele_count_by_locus gives them under the same mask; keep: one byte a genome (0 = left out) or NULL; Tot(c) =
+ * the sum of column c over the kept genomes.  With S_H, S_M, S_O the three sums of a (row, column):
+ *   N = c0 + c1 + c2,  Sx = c1 + 2 c2,  Sxx = c1 + 4 c2;  Sy = Tot(q) - S_O(q),  Sxy = S_H(q) + 2 S_M(q),  Syy = Tot(q^2) - S_O(q^2);
+ *   cov = N Sxy - Sx Sy,  vx = N Sxx - Sx^2,  vy = N Syy - Sy^2            (exact integers, 128-bit; vx vy - cov^2 in 256)
+ *   beta = cov / vx / 2^s,   t = sign(cov) * sqrt((N - 2) * cov^2 / (vx vy - cov^2)).
+ * NaN where N < 3, vx == 0 or vy == 0; +-inf where vx vy == cov^2.  The product adds no error of its own: kgx_assoc_columns decides
+ * the quantisation and nothing else does. */
+int kgx_assoc_statistics(const int64_t* sums /* [n_rows][2 * n_traits][3] */, const uint32_t* row_counts /* [n_rows][4] */,
+                         uint64_t n_rows, const int32_t* columns /* [2 * n_traits][G] */, const uint8_t* keep /* [G] or NULL */,
+                         uint64_t n_genomes, uint32_t n_traits, int scale_bits, double* beta /* [n_rows][n_traits] */,
+                         double* t /* [n_rows][n_traits] */);   /* host only */
+
 /* ---- K4: VariantDBVariant::populationSummary (kgl_variant_db_variant.cpp:234-279). */
 int kgx_population_summary(kgx_pop* pop, uint64_t out[4]);
 

@@ -135,7 +135,15 @@ _SIGNATURES = {
     "kgx_pair_scores_last": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "kgx_grm_tables": (C.c_int, [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kgx_grm_finish": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_void_p]),
+    "kgx_column_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "kgx_column_sums_last": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kgx_assoc_columns": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "kgx_assoc_statistics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p,
+                                       C.c_void_p]),
 }
+
+# kgx_column_sums (include/kgx.h): the largest column value
+COLUMN_MAX = 1 << 26
 
 # kgx_pair_scores (include/kgx.h): the largest table entry, and the rows one workgroup accumulates in int32 in one launch
 SCORE_MAX, SCORE_ACC_ROWS = 8128, 131072
@@ -612,6 +620,20 @@ class Population:
         check(lib().kgx_pair_scores(self._h, None if idx is None else ptr(idx), n_rows, ptr(tab), ptr(out)))
         return out
 
+    def column_sums(self, columns, rows=None, n_rows: int | None = None) -> np.ndarray:
+        """The sums of every per-genome column over the genomes of each kind in every listed row (kgx_column_sums; rows None = the
+        first n_rows rows, every row by default): int64 [n_rows][C][3], word k of [i][j] = sum of columns[j][g] over the genomes g
+        with code k + 1 (H, M, O) in row rows[i], exact.  columns: int32 [C][n_genomes], |entry| <= COLUMN_MAX."""
+        cols = np.ascontiguousarray(columns, dtype=np.int32)
+        idx = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32)
+        if n_rows is None:
+            n_rows = self.n_variants if idx is None else len(idx)
+        if cols.ndim != 2 or cols.shape[1] != self.n_genomes or (idx is not None and len(idx) < n_rows):
+            raise ValueError("columns must be [C][n_genomes] and rows needs n_rows entries")
+        out = np.zeros((n_rows, cols.shape[0], 3), dtype=np.int64)
+        check(lib().kgx_column_sums(self._h, None if idx is None else ptr(idx), n_rows, ptr(cols), cols.shape[0], ptr(out)))
+        return out
+
     def load_phase_plane(self, both_phases: np.ndarray, v0: int = 0) -> None:
         """both_phases: [rows][n_genomes] booleans -- the genome's copies of the row's variant sit on both phases."""
         bits = np.packbits(np.ascontiguousarray(both_phases, dtype=np.uint8), axis=1, bitorder="little")
@@ -736,6 +758,43 @@ def grm_finish(scores, n_genomes: int, scale_bits: int, rows_used: int) -> np.nd
     out = np.zeros(len(s), dtype=np.float64)
     check(lib().kgx_grm_finish(ptr(s), int(n_genomes), int(scale_bits), int(rows_used), ptr(out)))
     return out
+
+
+def column_sums_last() -> tuple[float, int, int]:
+    """(product kernel ms, batches of list positions, genome slices of the grid) of the last column_sums call (kgx_column_sums_last)."""
+    ms, batches, splits = C.c_double(0.0), C.c_uint64(0), C.c_uint64(0)
+    check(lib().kgx_column_sums_last(C.byref(ms), C.byref(batches), C.byref(splits)))
+    return float(ms.value), int(batches.value), int(splits.value)
+
+
+def assoc_columns(y, scale_bits: int = -1) -> tuple[np.ndarray, int]:
+    """kgx_assoc_columns: traits float64 [T][G] -> (columns int32 [2 T][G] = q = rint(y 2^s), then q^2; the scale_bits used).
+    scale_bits < 0: the largest s <= 12 at which every |q| <= 8128.  Host only."""
+    traits = np.ascontiguousarray(y, dtype=np.float64)
+    if traits.ndim != 2:
+        raise ValueError("y must be [n_traits][n_genomes]")
+    columns = np.zeros((2 * traits.shape[0], traits.shape[1]), dtype=np.int32)
+    bits = C.c_int(scale_bits)
+    check(lib().kgx_assoc_columns(ptr(traits), traits.shape[1], traits.shape[0], C.byref(bits), ptr(columns)))
+    return columns, int(bits.value)
+
+
+def assoc_statistics(sums, row_counts, columns, scale_bits: int, keep=None) -> tuple[np.ndarray, np.ndarray]:
+    """kgx_assoc_statistics: (beta, t) float64 [n_rows][T] of the regression of the quantised traits on the dosage over the called,
+    kept genomes of every row, from the column_sums table [n_rows][2 T][3] of assoc_columns' columns [2 T][G], the rows' code
+    counts [n_rows][4] (allele_count_by_locus under the same mask) and the mask's keep bytes [G] (None: every genome).  Host only."""
+    s = np.ascontiguousarray(sums, dtype=np.int64)
+    counts = np.ascontiguousarray(row_counts, dtype=np.uint32)
+    cols = np.ascontiguousarray(columns, dtype=np.int32)
+    kept = None if keep is None else np.ascontiguousarray(keep, dtype=np.uint8)
+    if cols.ndim != 2 or cols.shape[0] % 2 or s.shape != (len(counts), cols.shape[0], 3) or counts.shape != (len(counts), 4) or \
+            (kept is not None and kept.shape != (cols.shape[1],)):
+        raise ValueError("sums must be [n_rows][2 T][3], row_counts [n_rows][4], columns [2 T][G] and keep [G]")
+    traits = cols.shape[0] // 2
+    beta, t = np.zeros((len(counts), traits), dtype=np.float64), np.zeros((len(counts), traits), dtype=np.float64)
+    check(lib().kgx_assoc_statistics(ptr(s), ptr(counts), len(counts), ptr(cols), None if kept is None else ptr(kept), cols.shape[1], traits,
+                                     int(scale_bits), ptr(beta), ptr(t)))
+    return beta, t
 
 
 def gene_genotypes_last_ms() -> float:
