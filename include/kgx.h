@@ -561,6 +561,53 @@ int kgx_assoc_statistics(const int64_t* sums /* [n_rows][2 * n_traits][3] */, co
                          uint64_t n_genomes, uint32_t n_traits, int scale_bits, double* beta /* [n_rows][n_traits] */,
                          double* t /* [n_rows][n_traits] */);   /* host only */
 
+/* ---- Per-genome scores: class sums of per-row weights -- the genome x per-row-value product, the transpose of kgx_column_sums, that
+ *      a polygenic score, the projection of genomes onto principal-component loadings and an ancestry score are computed from; with
+ *      kgx_column_sums the two halves Z^T (Z v) of an iteration on the GRM.  The reference has no counterpart; these are THE LIBRARY'S
+ *      definitions.
+ * weights[j][i] is the caller's value of LIST POSITION i in column j (an effect size, a loading), |value| <= KGX_SCORE_MAX.  With
+ * code(g, r) the 2-bit code (1 = H, 2 = M, 3 = O / no-call):
+ *     out[g][j][k] = sum over the list positions i with code(g, rows[i]) == k + 1 of  weights[j][i]            (an exact int64)
+ * for every genome g of the WHOLE population.  The code-0 sum is not stored: for a kept genome it is the column's total minus the
+ * three stored sums.  rows as in kgx_column_sums: host [n_rows], any order, a row listed twice is two positions each with its own
+ * weight, NULL = rows 0 .. n_rows-1.  A caller who needs more than 14 bits splits a weight over two columns.
+ * KGX_EINVAL: |weights[j][i]| > KGX_SCORE_MAX (the message names j and i); a row >= n_variants; NULL rows with n_rows > n_variants;
+ * n_columns == 0 with n_rows > 0; n_rows >= 2^32; null pop or out, or null weights with n_rows > 0; a table whose byte size
+ * overflows 64 bits.  n_rows == 0 writes zeros.
+ * Exact: the columns are taken in groups of 16, each split into one or two signed base-128 digits (one where every value of the group
+ * lies in [-64, 63]: this affects speed only); the codes are transposed in registers, the indicator x digit products run int8 ->
+ * int32 on the matrix cores, at most KGX_GSCORE_ACC_ROWS rows into one int32 accumulation, and are put together in int64.  Honours
+ * the genome mask: a genome left out reads all zero.
+ * Works over any binding: every shard scores its own genomes from its own rows on its own device; nothing is exchanged between
+ * shards.  The result depends neither on the binding nor on batching nor on splitting.
+ * The shards' tables, the list, the weights (2 bytes a value), the group plan and a batch's digit operands come from the grow-only
+ * arena (kgx_release_scratch): list positions are processed in batches of whole 256-row segments when the operands would exceed a
+ * quarter of (free + arena) beside the rest.  KGX_GSCORE_ROWS=n caps the rows per batch (rounded up to a segment) and
+ * KGX_GSCORE_SPLITS=n the slices below (both read at kgx_init / kgx_reload_options; unset or <= 0: no effect; each only ever lowers
+ * a number). */
+#define KGX_GSCORE_ACC_ROWS 16777216   /* 2^24 rows into one int32 accumulation: 64 * 2^24 = 2^30 */
+int kgx_genome_scores(kgx_pop* pop, const uint32_t* rows /* host [n_rows] or NULL */, uint64_t n_rows,
+                      const int16_t* weights /* host [n_columns][n_rows], by LIST POSITION */, uint32_t n_columns,
+                      int64_t* out /* host [G][n_columns][3], G = the WHOLE population */);
+/* Of the last call: device time (HIP events; the slowest device's, summed over the batches) of the product kernel, the number of
+ * batches, and into how many slices the segments of a batch were split over the grid (1 = not split; more where a shard has fewer
+ * (256-genome block, group) pairs than two workgroups per compute unit -- the slices then add atomically).  Multiply-accumulates as
+ * the digits run it: 3 * G * n_rows * 16 * tiles. */
+int kgx_genome_scores_last(double* kernel_ms, uint64_t* row_batches, uint64_t* row_splits);
+/* Effect sizes as weights.  Host only, no device.  beta[j][i] is the effect of list position i in score j; weights[j] = q_j =
+ * llrint(beta_j * 2^s).  With row_counts (the listed rows' code counts as kgx_allele_count_by_locus gives them) the columns n_scores ..
+ * 2 n_scores - 1 hold m_j = llrint(2 p_i * beta_j * 2^s), p = (c1 + 2 c2) / (2 called) -- mean imputation of the no-calls: 2 p is ONE
+ * division (c1 + 2 c2) / called, times beta ONE multiplication; a row with called == 0 gets m = 0.  *scale_bits in: 0 .. 12, or < 0 =
+ * choose the largest s <= 12 at which every entry is within KGX_SCORE_MAX; out: the s used.  A non-finite beta, a given s at which an
+ * entry does not fit (the message names the score and the row), s > 12, or a null argument: KGX_EINVAL. */
+int kgx_score_weights(const double* beta /* [n_scores][n_rows] */, const uint32_t* row_counts /* [n_rows][4] or NULL */, uint64_t n_rows,
+                      uint32_t n_scores, int* scale_bits, int16_t* weights /* [n_scores or 2 * n_scores][n_rows] */);   /* host only */
+/* The scores.  Host only, no device.  sums: kgx_genome_scores of the weights of kgx_score_weights ([G][n_scores][3], imputed:
+ * [G][2 * n_scores][3]); out[g][j] = (S_H(q_j) + 2 S_M(q_j) + (imputed ? S_O(m_j) : 0)) / 2^s -- ONE conversion and ONE exact scaling.
+ * The result is EXACTLY the score of the quantised weights: kgx_score_weights decides the quantisation and nothing else does. */
+int kgx_score_finish(const int64_t* sums, uint64_t n_genomes, uint32_t n_scores, int imputed, int scale_bits,
+                     double* out /* [G][n_scores] */);   /* host only */
+
 /* ---- K4: VariantDBVariant::populationSummary (kgl_variant_db_variant.cpp:234-279). */
 int kgx_population_summary(kgx_pop* pop, uint64_t out[4]);
 

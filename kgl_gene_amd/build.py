@@ -33,12 +33,12 @@ HIP_FLAGS = [
     "-mllvm", "-amdgpu-mfma-vgpr-form",
 ]
 # Per translation unit, on top of HIP_FLAGS.  New units are compiled without gfx950's packed fp32 arithmetic (v_pk_add_f32,
-# v_pk_mul_f32, v_pk_fma_f32): kgx_roh.hip, kgx_pair_runs.hip, kgx_pair_scores.hip and kgx_assoc.hip, whose device code is integers
-# only (the middle two also compile k_pair_panel, integers too).  hipcc hands the feature to its host pass as well, which does not
-# know it and says that it ignores it.
+# v_pk_mul_f32, v_pk_fma_f32): kgx_roh.hip, kgx_pair_runs.hip, kgx_pair_scores.hip, kgx_assoc.hip and kgx_gscore.hip, whose device
+# code is integers only (the second and third also compile k_pair_panel, integers too).  hipcc hands the feature to its host pass as
+# well, which does not know it and says that it ignores it.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"kgx_roh.hip": _NO_PACKED_FP32, "kgx_pair_runs.hip": _NO_PACKED_FP32, "kgx_pair_scores.hip": _NO_PACKED_FP32,
-              "kgx_assoc.hip": _NO_PACKED_FP32}
+              "kgx_assoc.hip": _NO_PACKED_FP32, "kgx_gscore.hip": _NO_PACKED_FP32}
 OBJDIR = LIBDIR / "obj"
 
 

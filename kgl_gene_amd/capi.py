@@ -140,6 +140,10 @@ _SIGNATURES = {
     "kgx_assoc_columns": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "kgx_assoc_statistics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p,
                                        C.c_void_p]),
+    "kgx_genome_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "kgx_genome_scores_last": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kgx_score_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "kgx_score_finish": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
 }
 
 # kgx_column_sums (include/kgx.h): the largest column value
@@ -147,6 +151,9 @@ COLUMN_MAX = 1 << 26
 
 # kgx_pair_scores (include/kgx.h): the largest table entry, and the rows one workgroup accumulates in int32 in one launch
 SCORE_MAX, SCORE_ACC_ROWS = 8128, 131072
+
+# kgx_genome_scores (include/kgx.h): the rows of one int32 accumulation (its weights are within SCORE_MAX too)
+GSCORE_ACC_ROWS = 1 << 24
 
 # the modes of kgx_pair_runs (include/kgx.h)
 KGX_SHARE_IBS0, KGX_SHARE_IDENTICAL = 0, 1
@@ -634,6 +641,20 @@ class Population:
         check(lib().kgx_column_sums(self._h, None if idx is None else ptr(idx), n_rows, ptr(cols), cols.shape[0], ptr(out)))
         return out
 
+    def genome_scores(self, weights, rows=None, n_rows: int | None = None) -> np.ndarray:
+        """The sums of every per-row weight column over the listed rows of each kind in every genome (kgx_genome_scores; rows None =
+        the first n_rows rows): int64 [n_genomes][C][3], word k of [g][j] = sum of weights[j][i] over the list positions i where
+        genome g has code k + 1 (H, M, O) in row rows[i], exact.  weights: int16 [C][n_rows] by list position, |entry| <= SCORE_MAX."""
+        w = np.ascontiguousarray(weights, dtype=np.int16)
+        idx = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32)
+        if n_rows is None:
+            n_rows = (w.shape[1] if w.ndim == 2 else 0) if idx is None else len(idx)
+        if w.ndim != 2 or w.shape[1] != n_rows or (idx is not None and len(idx) < n_rows):
+            raise ValueError("weights must be [C][n_rows] and rows needs n_rows entries")
+        out = np.zeros((self.n_genomes, w.shape[0], 3), dtype=np.int64)
+        check(lib().kgx_genome_scores(self._h, None if idx is None else ptr(idx), n_rows, ptr(w), w.shape[0], ptr(out)))
+        return out
+
     def load_phase_plane(self, both_phases: np.ndarray, v0: int = 0) -> None:
         """both_phases: [rows][n_genomes] booleans -- the genome's copies of the row's variant sit on both phases."""
         bits = np.packbits(np.ascontiguousarray(both_phases, dtype=np.uint8), axis=1, bitorder="little")
@@ -795,6 +816,39 @@ def assoc_statistics(sums, row_counts, columns, scale_bits: int, keep=None) -> t
     check(lib().kgx_assoc_statistics(ptr(s), ptr(counts), len(counts), ptr(cols), None if kept is None else ptr(kept), cols.shape[1], traits,
                                      int(scale_bits), ptr(beta), ptr(t)))
     return beta, t
+
+
+def genome_scores_last() -> tuple[float, int, int]:
+    """(product kernel ms of the slowest device, batches of list positions, row slices of the grid) of the last genome_scores call
+    (kgx_genome_scores_last)."""
+    ms, batches, splits = C.c_double(0.0), C.c_uint64(0), C.c_uint64(0)
+    check(lib().kgx_genome_scores_last(C.byref(ms), C.byref(batches), C.byref(splits)))
+    return float(ms.value), int(batches.value), int(splits.value)
+
+
+def score_weights(beta, row_counts=None, scale_bits: int = -1) -> tuple[np.ndarray, int]:
+    """kgx_score_weights: effects float64 [S][n_rows] -> (weights int16 [S][n_rows] = q = rint(beta 2^s) -- with the listed rows' code
+    counts [n_rows][4] followed by S more columns m = rint(2 p beta 2^s), the mean imputation of no-calls; the scale_bits used).
+    scale_bits < 0: the largest s <= 12 at which every entry is within SCORE_MAX.  Host only."""
+    b = np.ascontiguousarray(beta, dtype=np.float64)
+    counts = None if row_counts is None else np.ascontiguousarray(row_counts, dtype=np.uint32)
+    if b.ndim != 2 or (counts is not None and counts.shape != (b.shape[1], 4)):
+        raise ValueError("beta must be [n_scores][n_rows] and row_counts [n_rows][4]")
+    weights = np.zeros(((1 if counts is None else 2) * b.shape[0], b.shape[1]), dtype=np.int16)
+    bits = C.c_int(scale_bits)
+    check(lib().kgx_score_weights(ptr(b), None if counts is None else ptr(counts), b.shape[1], b.shape[0], C.byref(bits), ptr(weights)))
+    return weights, int(bits.value)
+
+
+def score_finish(sums, n_scores: int, scale_bits: int, imputed: bool = False) -> np.ndarray:
+    """kgx_score_finish: float64 [G][S] = (S_H(q) + 2 S_M(q) + (imputed: S_O(m))) / 2^s from the genome_scores table [G][S or 2 S][3]
+    of score_weights' weights.  Host only."""
+    s = np.ascontiguousarray(sums, dtype=np.int64)
+    if s.ndim != 3 or s.shape[1:] != ((2 if imputed else 1) * n_scores, 3):
+        raise ValueError("sums must be [G][n_scores][3], imputed [G][2 n_scores][3]")
+    out = np.zeros((s.shape[0], n_scores), dtype=np.float64)
+    check(lib().kgx_score_finish(ptr(s), s.shape[0], int(n_scores), int(bool(imputed)), int(scale_bits), ptr(out)))
+    return out
 
 
 def gene_genotypes_last_ms() -> float:
