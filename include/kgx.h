@@ -608,6 +608,67 @@ int kgx_score_weights(const double* beta /* [n_scores][n_rows] */, const uint32_
 int kgx_score_finish(const int64_t* sums, uint64_t n_genomes, uint32_t n_scores, int imputed, int scale_bits,
                      double* out /* [G][n_scores] */);   /* host only */
 
+/* ---- Pairwise identity by descent by a two-state hidden Markov model: per genome pair the probability of the listed rows and the
+ *      expected (weighted) number of them at which the two genomes are IBD, given per-row emission tables and carry probabilities --
+ *      the result a cohort of haploid-like genomes is analysed with; kgx_pair_runs' IBS runs are its screen.  The reference has no
+ *      counterpart; these are THE LIBRARY'S definitions.
+ * Pairs: the unordered pairs a <= b of the WHOLE population at kgx_pair_counts' pair index a*G - a*(a-1)/2 + (b - a).  rows as in
+ * kgx_pair_runs: host [n_rows], any order, a row listed twice is two positions, NULL = rows 0 .. n_rows-1.
+ * States: 0 = not IBD, 1 = IBD.
+ * Cell, for one pair and list position i, ca and cb the two codes: NEUTRAL (e0 = e1 = 1) if either is 3; otherwise with x = min(ca, cb),
+ * y = max(ca, cb) the class k = 3x - x(x-1)/2 + (y - x) -- (0,0) (0,1) (0,2) (1,1) (1,2) (2,2) = 0 .. 5 -- and e_s = (double)emit[i][s][k].
+ * Transition: rho_i = carry[i], the probability that nothing switched between list positions i-1 and i; rho_0 is taken as 0 whatever
+ * carry[0] holds; a contig start is a carry of 0.  In double: c1_i = (1 - rho_i) * pi, c0_i = (1 - rho_i) * (1 - pi).  w_i = weight[i],
+ * or 1 with weight == NULL.
+ * Recursion, from F0 = 1 - pi, F1 = pi, V0 = V1 = 0, for i = 0 .. n_rows-1 (every term is non-negative: the error bound rests on it):
+ *     S = F0 + F1;  SV = V0 + V1
+ *     P1 = rho F1 + c1 S;   P0 = rho F0 + c0 S;   Q1 = rho V1 + c1 SV;   Q0 = rho V0 + c0 SV
+ *     F1 = e1 P1;   F0 = e0 P0;   V1 = e1 Q1 + w_i F1;   V0 = e0 Q0
+ * Result: out[pair] = { loglik = ln(F0 + F1), ibd = (V0 + V1) / (F0 + F1) }.  ibd equals sum_i w_i P(state_i = IBD | ALL rows): V
+ * carries the weight already collected forward with the path, so no backward pass is run and nothing per row is stored.
+ * Arithmetic: fp64.  Each "a b + c" above is one fused multiply-add or a multiply and an add.  F and V share one power-of-two scale
+ * per pair with an integer exponent E: after every 16th list position (15, 31, ..) and after the last, the four values are multiplied
+ * by 2^-k, k = the binary exponent of F0 + F1, and E += k -- exact, and at FIXED list positions, so the result is bit for bit the
+ * same under any binding and any row batching; loglik = ln(F0 + F1) + E ln 2.  With the ranges below F0 + F1 moves by at most 2^+-480
+ * between two rescales.  A component more than 2^-500 below its pair's sum may lose bits or vanish; its share of either result is
+ * below that.  Per step the relative error of F grows by at most 6 u and that of V by at most 8 u (u = 2^-53).
+ * KGX_EINVAL (the message names the index): an emit entry that is not finite or outside [2^-30, 2^30]; carry[i] outside [0, 1];
+ * weight[i] negative, not finite or above 2^32; pi outside the open interval (0, 1); a row >= n_variants; NULL rows with n_rows >
+ * n_variants; n_rows >= 2^32; null pop or params, or null emit, carry or out with n_rows > 0.
+ * n_rows == 0 writes {0, 0}.  Every pair that involves a genome the mask leaves out reads {0, 0}.  The diagonal pair (a, a) follows
+ * the same rule.
+ * Works over any binding like kgx_pair_runs: every shard turns the listed rows of its genomes into kgx_pair_counts' genome-major panel
+ * on its device, the panels are copied behind one another on the FIRST slot's device and the walk runs there, one workgroup per pair
+ * of 32-genome tiles for the whole list.  The table (56 bytes a pair: the state between two batches and the result), the list's
+ * tables (80 bytes a row) and one panel batch come from the grow-only arena (kgx_release_scratch): rows are processed in batches of
+ * whole 64-row tiles when the panel would exceed a quarter of (free + arena) on a device; a table that does not fit beside one 64-row
+ * panel: KGX_ENOMEM.  KGX_PAIR_HMM_ROWS=n (read at kgx_init / kgx_reload_options; unset or <= 0: no effect; it only ever lowers the
+ * number) caps the rows per batch, rounded up to 64. */
+typedef struct kgx_pair_hmm_params { double pi; } kgx_pair_hmm_params;      /* prior IBD share, 0 < pi < 1 */
+typedef struct kgx_pair_hmm_result { double loglik, ibd; } kgx_pair_hmm_result;
+int kgx_pair_hmm(kgx_pop* pop, const uint32_t* rows /* host [n_rows] or NULL */, uint64_t n_rows,
+                 const float* emit /* host [n_rows][2][6] */, const double* carry /* host [n_rows] */,
+                 const double* weight /* host [n_rows] or NULL = all 1 */, const kgx_pair_hmm_params* params,
+                 kgx_pair_hmm_result* out /* host [G(G+1)/2] */);
+/* Of the last call: device time (HIP events, summed over the row batches) of the walk kernel, and the number of row batches.
+ * Steps of the recursion: G(G+1)/2 * n_rows. */
+int kgx_pair_hmm_last(double* kernel_ms, uint64_t* row_batches);
+/* Emission tables of the biallelic haploid model.  Host only, no device.  row_counts[i] = the counts of codes 0 .. 3 of LISTED row i.
+ * Code 0 is allele 0, code 2 is allele 1; a het is uninformative: the classes k = 1, 3, 4 are 1 in both states.  With p_1 = c2 / (c0 +
+ * c2), p_0 = 1 - p_1, the error rate eps, P(x | z) = 1 - eps if x == z else eps, and g(x) = p_x (1 - eps) + (1 - p_x) eps:
+ *     e0(x, y) = g(x) g(y)                                   (two independent draws)
+ *     e1(x, y) = sum over z of p_z P(x | z) P(y | z)         (one draw, observed twice)
+ * for (x, y) = (0,0), (0,1), (1,1) at k = 0, 2, 5; each state's table sums to 1 over the four ORDERED allele pairs: e[k=0] + 2 e[k=2] +
+ * e[k=5] = 1.  A row with c0 + c2 == 0, c0 == 0 or c2 == 0 gets all ones.  Computed in double, then ONE rounding to float.
+ * KGX_EINVAL: eps outside (0, 0.5]; a null argument with n_rows > 0. */
+int kgx_ibd_tables(const uint32_t* row_counts /* [n_rows][4] */, uint64_t n_rows, double eps, float* emit /* [n_rows][2][6] */);   /* host only */
+/* Carry probabilities from positions.  Host only, no device.  carry[i] = exp(-rate * (position[i] - position[i-1])) -- one
+ * multiplication and one exp, in double -- and 0 at i == 0 and where contig_start[i] != 0 (NULL: one contig).  KGX_EINVAL as in
+ * kgx_roh: position[i] < position[i-1] without a contig start at i (the message names i); a rate that is negative or not finite; a
+ * null position or carry with n_rows > 0. */
+int kgx_ibd_carry(const uint32_t* position /* [n_rows] */, const uint8_t* contig_start /* [n_rows] or NULL */, uint64_t n_rows, double rate,
+                  double* carry /* [n_rows] */);   /* host only */
+
 /* ---- K4: VariantDBVariant::populationSummary (kgl_variant_db_variant.cpp:234-279). */
 int kgx_population_summary(kgx_pop* pop, uint64_t out[4]);
 

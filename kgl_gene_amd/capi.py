@@ -144,6 +144,10 @@ _SIGNATURES = {
     "kgx_genome_scores_last": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "kgx_score_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "kgx_score_finish": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
+    "kgx_pair_hmm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kgx_pair_hmm_last": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kgx_ibd_tables": (C.c_int, [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p]),
+    "kgx_ibd_carry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_void_p]),
 }
 
 # kgx_column_sums (include/kgx.h): the largest column value
@@ -613,6 +617,24 @@ class Population:
                                   ptr(out)))
         return out
 
+    def pair_hmm(self, emit, carry, rows=None, n_rows: int | None = None, weight=None, pi: float = 0.5) -> np.ndarray:
+        """Identity by descent of every genome pair a <= b along the listed rows by the two-state HMM of kgx_pair_hmm (rows None = the
+        first n_rows rows): float64 [G (G + 1) / 2][2] = {loglik, ibd} at pair_index(a, b, G); ibd = sum over list positions of weight *
+        P(IBD | all rows).  emit: float32 [n_rows][2][6] (ibd_tables), carry: float64 [n_rows] (ibd_carry), weight: float64 [n_rows] or
+        None = all 1, pi: the prior IBD share."""
+        tab = np.ascontiguousarray(emit, dtype=np.float32)
+        keep = np.ascontiguousarray(carry, dtype=np.float64)
+        idx = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32)
+        w = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64)
+        n_rows = int(n_rows if n_rows is not None else (len(keep) if idx is None else len(idx)))
+        if tab.shape[1:] != (2, 6) or min(len(tab), len(keep)) < n_rows or (idx is not None and len(idx) < n_rows) or (w is not None and len(w) < n_rows):
+            raise ValueError("emit must be [n_rows][2][6]; carry, rows and weight need n_rows entries each")
+        params = np.array([pi], dtype=np.float64)
+        out = np.zeros((self.n_genomes * (self.n_genomes + 1) // 2, 2), dtype=np.float64)
+        check(lib().kgx_pair_hmm(self._h, None if idx is None else ptr(idx), n_rows, ptr(tab), ptr(keep), None if w is None else ptr(w), ptr(params),
+                                 ptr(out)))
+        return out
+
     def pair_scores(self, tables, rows=None, n_rows: int | None = None) -> np.ndarray:
         """The score of every genome pair a <= b over the listed rows (kgx_pair_scores; rows None = the first n_rows rows): int64
         [G (G + 1) / 2] at pair_index(a, b, G) = sum over list positions i of tables[i][code of a] * tables[i][code of b], exact.
@@ -750,6 +772,35 @@ def pair_run_fractions(summary, n_genomes: int, denominator: int) -> np.ndarray:
     out = np.zeros(len(s), dtype=np.float64)
     check(lib().kgx_pair_run_fractions(ptr(s), int(n_genomes), int(denominator), ptr(out)))
     return out
+
+
+def pair_hmm_last() -> tuple[float, int]:
+    """(walk kernel ms summed over the row batches, row batches) of the last pair_hmm call (kgx_pair_hmm_last)."""
+    ms, batches = C.c_double(0.0), C.c_uint64(0)
+    check(lib().kgx_pair_hmm_last(C.byref(ms), C.byref(batches)))
+    return ms.value, batches.value
+
+
+def ibd_tables(row_counts, eps: float) -> np.ndarray:
+    """kgx_ibd_tables: the emission tables float32 [n_rows][2][6] of the biallelic haploid model from the listed rows' code counts
+    [n_rows][4] and the genotyping error rate.  Host only."""
+    counts = np.ascontiguousarray(row_counts, dtype=np.uint32)
+    if counts.ndim != 2 or counts.shape[1] != 4:
+        raise ValueError("row_counts must be [n_rows][4]")
+    emit = np.zeros((len(counts), 2, 6), dtype=np.float32)
+    check(lib().kgx_ibd_tables(ptr(counts), len(counts), float(eps), ptr(emit)))
+    return emit
+
+
+def ibd_carry(position, rate: float, contig_start=None) -> np.ndarray:
+    """kgx_ibd_carry: float64 [n_rows] = exp(-rate * step in bases), 0 at index 0 and at contig starts.  Host only."""
+    pos = np.ascontiguousarray(position, dtype=np.uint32)
+    starts = None if contig_start is None else np.ascontiguousarray(contig_start, dtype=np.uint8)
+    if starts is not None and len(starts) < len(pos):
+        raise ValueError("contig_start needs an entry per position")
+    carry = np.zeros(len(pos), dtype=np.float64)
+    check(lib().kgx_ibd_carry(ptr(pos), None if starts is None else ptr(starts), len(pos), float(rate), ptr(carry)))
+    return carry
 
 
 def pair_scores_last() -> tuple[float, int, int]:
